@@ -8,16 +8,26 @@ compression of the whole batch followed by one decompression of what it just
 produced; value = uncompressed bytes of every rank / max-over-ranks wall time
 of the steps, in GiB/s (so value = n / (t_compress + t_decompress)).
 
-Also on the line: the decode-only rate of the same batch (configs[1], C2,
-timed on its own), the HBM roofline of each kernel (`roofline` is the decoder,
-whose roofline fraction the north star targets; `compress_roofline` the
-encoder, the larger share of a step), and the reference's own lib/minilzo.c
-(oracle/_ref, compiled from the reference sources) on this box's host cores:
-a bounded sample of the same ITB blocks, whose compressed bytes are also
-compared with the GPU's (C3 byte identity), and configs[0] (C1: random 64
-KiB blocks, compress -> decompress round trip on the CPU).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what that figure
+needs and no more: it generates the batch, warms up, times the N steps, checks
+the last step's round trip on the device and prints the line, with the HBM
+roofline of each kernel from the HIP events of the timed steps (`roofline` is
+the decoder, whose roofline fraction the north star targets;
+`compress_roofline` the encoder, the larger share of a step).
+`--dump-outputs DIR` also writes what the last timed step returned
+(dump_outputs below).
 
-Other workloads (--workload):
+`--full` adds, each in a run of its own after the timed steps: the decode-only
+rate of the same batch (configs[1], C2), a measured device-to-device copy
+beside the rooflines, the two-stream pipelined legs, C4, C5 and the single
+calls (`other_configs`), and the reference's own lib/minilzo.c (oracle/_ref,
+compiled from the reference sources) on the host cores: a bounded sample of
+the same ITB blocks, whose compressed bytes are also compared with the GPU's
+(C3 byte identity), and configs[0] (C1: random 64 KiB blocks, compress ->
+decompress round trip on the CPU).
+
+Other workloads (--workload; each reports all it measures, with or without
+--full):
   c2  decompress-only steps (configs[1])
   c4  mixed 4-256 KiB ITB blocks, decompress GiB/s; --c4-blocks per GPU
       (default 131072 = 1 M / 8: the 8-GPU run is exactly configs[3])
@@ -64,8 +74,18 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-others", action="store_true",
-                   help="C3 at N=1: skip the C4 and C5 measurements reported beside the headline")
-    return p.parse_args()
+                   help="C3 with --full: skip the C4 and C5 measurements reported beside the headline")
+    p.add_argument("--full", action="store_true",
+                   help="C3: also measure what is reported beside the headline (decode-only and "
+                        "pipelined legs, measured copy bandwidth, CPU baselines, C4, C5, single calls)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="c2/c3/c4: write what the last timed step returned as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload in ("c5", "single"):
+        p.error("--dump-outputs covers the device-resident workloads (c2, c3, c4)")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -498,6 +518,54 @@ def roofline(kind, nbytes, kernel_s, block_bytes, nblocks, note):
             "kernel": note}
 
 
+DUMP_SEED = 20241                       # the block and byte sample of --dump-outputs
+DUMP_ARRAY_BYTES = 16 << 20             # per sampled array; three of them plus the per-block ones < 64 MB
+
+
+def dump_outputs(R, directory, compressed):
+    """What a caller of the timed step receives, as float .npy files (the
+    inputs are seeded, so two builds can be compared array for array):
+      decompressed_length, decompress_status    every block (float64)
+      decompressed_blocks   a fixed seeded sample of whole blocks, one row each,
+                            zero beyond the block's length (float32)
+      decompressed_bytes    a fixed seeded sample of byte positions of the
+                            whole output arena (float32)
+    and where the step compresses (C3) the same for the compressed side:
+      compressed_length, compress_status, compressed_blocks (the same sampled
+      blocks; each row is the block's stream, zero beyond its length).
+    The block sample is as many blocks as fit DUMP_ARRAY_BYTES at the widest
+    block's compressed capacity."""
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    nb = len(R.sizes)
+    caps = R.zdst.length.cpu().numpy().astype(np.int64)
+    k = max(1, min(nb, DUMP_ARRAY_BYTES // (4 * int(caps.max()))))
+    idx = np.sort(rng.choice(nb, size=k, replace=False))
+    pos = np.sort(rng.integers(0, R.out.numel(), size=min(R.out.numel(), DUMP_ARRAY_BYTES // 4)))
+
+    def save(name, a, dtype):
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a).astype(dtype))
+
+    def rows(arena, off, length, width):
+        a = np.zeros((k, width), dtype=np.float32)
+        for j, b in enumerate(idx):
+            o, n = int(off[b]), int(length[b])
+            a[j, :n] = arena[o: o + n].cpu().numpy()
+        return a
+
+    off = R.src.off.cpu().numpy()
+    olen = R.olen.cpu().numpy()
+    save("decompressed_length", olen, np.float64)
+    save("decompress_status", R.ost.cpu().numpy(), np.float64)
+    save("decompressed_blocks", rows(R.out, off, olen, int(R.sizes.max())), np.float32)
+    save("decompressed_bytes", R.out[R.torch.from_numpy(pos).to(R.dev)].cpu().numpy(), np.float32)
+    if compressed:
+        zlen = R.zlen.cpu().numpy()
+        save("compressed_length", zlen, np.float64)
+        save("compress_status", R.zst.cpu().numpy(), np.float64)
+        save("compressed_blocks", rows(R.zdst.arena, R.zoffs, zlen, int(caps.max())), np.float32)
+
+
 def run_resident(args, torch, dist, lzo, synth, shard, dev, world, rank, backend):
     model = {v: k for k, v in synth.MODEL_NAMES.items()}[args.model]
     if args.workload in ("c2", "c3"):
@@ -522,21 +590,31 @@ def run_resident(args, torch, dist, lzo, synth, shard, dev, world, rank, backend
     errors = R.errors()
     n_bytes, z_bytes = R.n_bytes, R.z_bytes
     bb = args.block_bytes if args.workload != "c4" else None
+    # what is measured beside the headline, in runs of their own: always for
+    # c2 / c4 (they are asked for by name), for C3 only with --full
+    full = args.workload != "c3" or args.full
+    dump = args.dump_outputs if rank == 0 else None      # (rank 0's share)
     # headline: C3 steps (compress, then decompress what it produced), or
     # decompress-only steps for c2 / c4
     if args.workload == "c3":
         wall, (t_c, t_d) = timed(torch, dist, world, stream, [R.compress, R.decompress],
                                  args.steps, args.warmup)
         errors += R.errors()                               # the last step's round trip
-        dec_wall, (t_d2,) = timed(torch, dist, world, stream, [R.decompress], args.steps, 1)
+        if dump:
+            dump_outputs(R, dump, compressed=True)
+        if full:
+            dec_wall, _ = timed(torch, dist, world, stream, [R.decompress], args.steps, 1)
     else:
         wall, (t_d,) = timed(torch, dist, world, stream, [R.decompress], args.steps, args.warmup)
-        dec_wall, t_d2 = wall, t_d
+        if dump:
+            dump_outputs(R, dump, compressed=False)
+        dec_wall = wall
         comp_wall, (t_c,) = timed(torch, dist, world, stream, [R.compress], args.compress_steps, 1)
         errors += int((R.ost != 0).sum().item()) + int((R.zst != 0).sum().item())
     if dist_on(dist):
         errors, wall = shard.completion_barrier(dist, dev, errors, wall)
-        _, dec_wall = shard.completion_barrier(dist, dev, 0, dec_wall)
+        if full:
+            _, dec_wall = shard.completion_barrier(dist, dev, 0, dec_wall)
         if args.workload != "c3":
             _, comp_wall = shard.completion_barrier(dist, dev, 0, comp_wall)
         tot = torch.tensor([n_bytes, z_bytes], dtype=torch.float64,
@@ -546,7 +624,6 @@ def run_resident(args, torch, dist, lzo, synth, shard, dev, world, rank, backend
     else:
         n_all, z_all = n_bytes, z_bytes
     value = n_all * args.steps / wall / GIB
-    dec_gibps = n_all * args.steps / dec_wall / GIB
     nb = len(mine)
     if args.workload == "c3":
         metric = METRIC
@@ -577,26 +654,28 @@ def run_resident(args, torch, dist, lzo, synth, shard, dev, world, rank, backend
                                       "lzo1x_encode_gdict1_kernel" if "enc_waves=2" not in os.environ.get("POM_LZO_DEBUG", "")
                                       else "lzo1x_encode_gdict_kernel"),
         "step_ms": {"compress": round(t_c * 1e3, 4), "decompress": round(t_d * 1e3, 4)},
-        "decompress_gibps": round(dec_gibps, 3),
         "compress_kernel_gibps": round(n_bytes / t_c / GIB, 3),      # this GPU, HIP events
         "errors": errors,
         "fallback_blocks": R.fallback_blocks,
     }
     # whole-job HBM fraction over every GPU of the run:
     # algorithmic bytes of all ranks over the max-over-ranks time, against
-    # G x 8 TB/s -- decode alone, and both kernels of the round trip
-    agg = {"gpus": world, "peak_GBps_per_gpu": HBM_PEAK_GBPS,
-           "decode_frac": round((z_all + n_all) * args.steps / dec_wall / 1e9 / (world * HBM_PEAK_GBPS), 4)}
+    # G x 8 TB/s -- both kernels of the round trip, and (below) decode alone
+    agg = {"gpus": world, "peak_GBps_per_gpu": HBM_PEAK_GBPS}
+    result["aggregate_hbm"] = agg
     if args.workload == "c3":
         agg["roundtrip_frac"] = round(2 * (z_all + n_all) * args.steps / wall / 1e9 / (world * HBM_PEAK_GBPS), 4)
-    else:
+    if not full:
+        return result, errors
+    result["decompress_gibps"] = round(n_all * args.steps / dec_wall / GIB, 3)
+    agg["decode_frac"] = round((z_all + n_all) * args.steps / dec_wall / 1e9 / (world * HBM_PEAK_GBPS), 4)
+    if args.workload != "c3":
         # the metric's own quantity on this workload: compress + decompress of
         # every byte, whole job (each leg's max-over-ranks wall time per pass)
         t_rt = comp_wall / args.compress_steps + dec_wall / args.steps
         result["roundtrip_gibps"] = round(n_all / t_rt / GIB, 3)
         result["compress_gibps"] = round(n_all * args.compress_steps / comp_wall / GIB, 3)
         agg["roundtrip_frac"] = round(2 * (z_all + n_all) / t_rt / 1e9 / (world * HBM_PEAK_GBPS), 4)
-    result["aggregate_hbm"] = agg
     copy = copy_gbps(torch, dev)
     for key in ("roofline", "compress_roofline"):
         result[key]["copy_GBps_measured"] = round(copy, 1)
@@ -900,6 +979,7 @@ def run_others(args, torch, dist, lzo, synth, shard, dev, world, rank, backend):
     torch.cuda.empty_cache()
     a = copy.copy(args)
     a.workload, a.steps, a.warmup, a.compress_steps, a.no_cpu = "c4", 3, 1, 1, True
+    a.dump_outputs = None                          # (the dump is the headline's)
     try:
         r, e = run_resident(a, torch, dist, lzo, synth, shard, dev, world, rank, backend)
         out["c4"] = {"workload": r["config"]["workload"], "n_gpus": world,
@@ -1002,7 +1082,7 @@ def main():
     else:
         result, errors = run_resident(args, torch, dist, lzo, synth, shard, dev, world, rank,
                                       backend)
-        if args.workload == "c3" and not args.no_others:
+        if args.workload == "c3" and args.full and not args.no_others:
             result["other_configs"] = run_others(args, torch, dist, lzo, synth, shard, dev, world,
                                                  rank, backend)
             errors += sum(o.get("errors", 1) for o in result["other_configs"].values())

@@ -6,7 +6,7 @@ mkdir -p $O
 for r in 1 2 3; do
   for v in cpu nocpu; do
     a=""; [ $v = nocpu ] && a="--no-cpu"
-    timeout -k 10 300 python bench.py $a > $O/${v}_$r.log 2>&1 || { echo "$v run $r failed"; tail -5 $O/${v}_$r.log; exit 1; }
+    timeout -k 10 300 python bench.py --full $a > $O/${v}_$r.log 2>&1 || { echo "$v run $r failed"; tail -5 $O/${v}_$r.log; exit 1; }
     python - $O/${v}_$r.log $v $r <<'PY'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]) if l.startswith('{"metric"')][-1])

@@ -168,7 +168,8 @@ def _rccl_worker(port, q):
             barrier = shard.completion_barrier(dist, dev, 3, 1.25)
             args = argparse.Namespace(workload="c4", c4_blocks=256, steps=2, warmup=1,
                                       compress_steps=1, model="itb", block_bytes=65536,
-                                      blocks=4096, no_cpu=True, cpu_seconds=0.0)
+                                      blocks=4096, no_cpu=True, cpu_seconds=0.0, full=False,
+                                      dump_outputs=None)
             lzo.load()
             res, errors = bench.run_resident(args, torch, dist, lzo, synth, shard, dev, 1, 0,
                                              "nccl")
@@ -222,8 +223,10 @@ def test_bench_gpus_n_without_launcher_starts_n_ranks():
 def test_bench_gpus_n_never_reports_one_gpu():
     """Without a GPU the ranks fail, and so does the whole run: no one-GPU
     JSON line for a two-GPU request; a WORLD_SIZE that disagrees with --gpus
-    is refused."""
-    r = _bench(["--gpus", "2"], {"POM_DIST_BACKEND": "gloo"})
+    is refused.  The ranks are shown no device, so the test reads the same
+    on a machine that has one."""
+    r = _bench(["--gpus", "2"], {"POM_DIST_BACKEND": "gloo", "HIP_VISIBLE_DEVICES": "-1",
+                                 "CUDA_VISIBLE_DEVICES": "-1"})
     assert r.returncode != 0
     assert '"n_gpus": 1' not in r.stdout
     r = _bench(["--gpus", "4"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0",
