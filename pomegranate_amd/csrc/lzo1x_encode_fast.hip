@@ -10,12 +10,15 @@
 //    lane probes its own position against the dictionary as it was before the
 //    window (u16 positions in LDS, 0 = empty: the reference never stores
 //    position 0).  A lane's probe is exact as long as no earlier lane of the
-//    window that really probes writes a slot it reads.  Path lanes post
-//    (window tag, lane) for the slot they write into a claim table with
-//    ds_min, then read back the entries of the slots they read: an entry of
-//    this window from a lower lane is such a write (or, rarely, another slot
-//    hashing to the same entry), and the window is cut at the first lane that
-//    finds one, so every lane before it is exact.  Within
+//    window that really probes writes a slot it reads.  Every active lane
+//    posts (window tag, lane) for the slot it would write into a claim table
+//    with ds_min, once per window, and reads back the entries of the slots it
+//    read: an entry of this window from a lower lane flags it (a superset of
+//    such writes: the poster may be off the path, or another slot hashing to
+//    the same entry).  A flagged path lane that does have a writer below it
+//    is decided again from that writer's bytes, a few per window, and the
+//    window is cut at the next flagged lane, so every lane before it is
+//    exact.  Within
 //    the exact prefix the greedy parse proceeds as the reference does: the
 //    first matching lane emits a match, the lanes it covers are skipped (they
 //    neither probe nor update the dictionary), and the lane right after it
@@ -106,7 +109,7 @@ struct __attribute__((aligned(16))) EncLdsT {
     // entries stay only to keep the measured layout)
     uint16_t dict[GD ? 2 : kSlots + 2]; // last probe position per hash slot: position - base + 1 (0 = empty)
     uint32_t occ[GD && POM_ENC_OCC ? kSlots / 32 : 1];  // global dictionary: the slots this block wrote
-    uint32_t claim[kClaim + 1];     // (window tag << 8 | lowest writing lane) per hashed slot
+    uint32_t claim[kClaim + 1];     // (window tag << 8 | lowest posting lane) per hashed slot
     uint4 tok[kTok + 1];            // {literal start, literal count, match length (0: tail), offset}
     uint8_t stage[kStage];          // emitter output ring
     uint32_t prod;                  // tokens published by the parse wave
@@ -539,9 +542,14 @@ struct Emitter {
 // ---------------------------------------------------------------------------
 // Diagnostic build only (STAMPS): per-phase s_memtime cycle sums and counts of
 // the parse wave go to stamps[b * kEncStampSlots + i]; no output depends on them.
+// EP_CLAIM: the claim reads up to the first conflict mask; EP_FWDR: the
+// forwarding rounds after it.  EC_FALSE: flagged lanes with no writer.
+// EC_HWID, EC_XCC (one-wave kernel): the HW_ID and XCC_ID registers of the
+// wave that ran the block -- which CU of which XCD.
 enum { EP_SETUP, EP_PROBE, EP_CAND, EP_PATH, EP_CLAIM, EP_TOK, EP_DICT, EP_PUSHWAIT,
-       EC_WINDOWS, EC_EXTEND, EC_TOKENS, EC_PATHIT, EC_EXTIT, EC_C2NEED, EC_C2MATCH, EC_FWD, EP_N };
-constexpr int kEncStampSlots = 16;
+       EC_WINDOWS, EC_EXTEND, EC_TOKENS, EC_PATHIT, EC_EXTIT, EC_C2NEED, EC_C2MATCH, EC_FWD,
+       EP_FWDR, EC_FALSE, EC_HWID, EC_XCC, EP_N };
+constexpr int kEncStampSlots = 24;
 
 // FUSED (one-wave kernel): the parse wave runs the emitter E itself -- it
 // drains the token queue once POM_ENC_DRAIN tokens are pending (larger emit
@@ -733,6 +741,18 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                 acc[EC_C2MATCH] += 0;
             }
             ESTAMP(EP_CAND);
+            // ---- claims: one post per window, from every active lane ---------
+            // (tag, lane) for the slot the lane would write, whether or not the
+            // path reaches it, and the entries of the two slots it read.  The
+            // reads are consumed after the first walk (exactness, below), so
+            // their LDS latency overlaps the walk and its extension loads
+            // (posting after the walk: C3 compress +0.6%).  A wave's LDS
+            // operations complete in order, so the reads see every post.
+            if (active)
+                atomicMin(&S.claim[claim_index(slot)], (wtag << 8) | l);
+            wave_order();
+            const uint32_t t1 = S.claim[claim_index(h1)];
+            const uint32_t t2 = S.claim[claim_index(h2)];
             uint64_t path = 0, mstart = 0;
             uint32_t end = 0;                        // lane where the path leaves the window
             uint32_t nmatch = 0;
@@ -788,45 +808,51 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
             if (FUSED)
                 load_at<kCmpW, POM_PW_AUX>(B, ip + end0 + l, npw);
             ESTAMP(EP_PATH);
-            // ---- exactness: claims among the path lanes, and forwarding ------
-            // Path lane l read h1 (and h2 when use2) and writes slot.  The
-            // table keeps, per hashed slot, the lowest lane of this window
-            // writing it (ds_min of tag|lane; a wave's LDS operations complete
-            // in order, so the reads below see every post).  A path lane is
-            // inexact only if a lower path lane writes a slot it read.  Such a
-            // lane c, lowest first, is decided again: its entry is the position
-            // of the last lower path lane j writing that slot -- less than 64
-            // back, so the candidate passes the M2_MAX_OFFSET test -- and j's
-            // probe words are the candidate's bytes.  The path is walked again
-            // from c and the claims re-posted under a new tag.  After
-            // POM_ENC_FWD rounds the window ends at the next conflicting lane.
+            // ---- exactness: fixed per-lane flags, and forwarding ---------------
+            // Path lane l read h1 (and h2 when use2) and writes slot; it is
+            // inexact only if a lower path lane writes a slot it read.  The
+            // table keeps, per hashed slot, the lowest active lane of this
+            // window that posted it, so "the lowest poster of a slot I read is
+            // below me" (f1 for h1, f2 for h2) holds for every reader of a
+            // slot that a lower path lane writes as posted -- and for more
+            // lanes: a poster the path never reaches, or another slot hashing
+            // to the same entry.  The flags do not depend on the path, so a
+            // round is register work: the lowest flagged unresolved path lane
+            // c looks for its writer among the path lanes below it by their
+            // current slot.  None: a false alarm, c was exact.  Else c is
+            // decided again: its entry is the position of the last lower path
+            // lane j writing that slot -- less than 64 back, so the candidate
+            // passes the M2_MAX_OFFSET test -- and j's probe words are the
+            // candidate's bytes; the path is walked again from c.
+            // What a round changes: (1) the path at and above c -- lanes
+            // joining it posted like every active lane, so their flags already
+            // stand; (2) lane c's reads -- c is resolved, and the lanes below
+            // it no longer change, and um2 only loses bits; (3) lane c's written
+            // slot, when it read h2 before and now takes h1, which c did not
+            // post.  It moved there because a path lane j below it writes
+            // that slot: j posted it, or moved to it the same way from a
+            // lower lane still -- so some lane below c posted it, and every
+            // reader above c is flagged already.  No mask of late readers is
+            // needed (scripts/dbg/enc_claims_sim.c asserts that on every
+            // such move).  After POM_ENC_FWD forwardings the window ends at
+            // the next flagged lane (a false alarm there only makes it
+            // shorter).
             uint64_t resolved = 0, superseded = 0;   // (superseded: a later lane writes its slot)
             uint64_t um2 = wave_ballot(use2);        // lanes that read the secondary slot
-            for (uint32_t round = 0;; round++) {
-                const bool onpath = (path >> l) & 1ull;
-                const uint32_t mine = (wtag << 8) | l;
-                // (off-path lanes post nothing: sent to one spare entry, their
-                // atomics serialised on it -- lone 64 KiB 655 -> 640 us)
-                if (onpath)
-                    atomicMin(&S.claim[claim_index(slot)], mine);
-                wave_order();
-                const uint32_t t1 = S.claim[claim_index(h1)];
-                const uint32_t t2 = S.claim[claim_index(h2)];
-                // path lanes not yet resolved that read a slot a lower lane of
-                // this window writes (h1, or h2 when use2)
-                const uint64_t cf1 = mask_eq(t1 >> 8, wtag) & mask_lt(t1 & 0xFFu, l);
-                const uint64_t cf2 = um2 & mask_eq(t2 >> 8, wtag) & mask_lt(t2 & 0xFFu, l);
-                uint64_t cm = path & ~resolved & (cf1 | cf2);
-                wtag--;
+            const uint64_t f1 = mask_eq(t1 >> 8, wtag) & mask_lt(t1 & 0xFFu, l);
+            const uint64_t f2 = mask_eq(t2 >> 8, wtag) & mask_lt(t2 & 0xFFu, l);
+            wtag--;
+            for (uint32_t fwd = 0, first = 1;; first = 0) {
+                const uint64_t cm = path & ~resolved & (f1 | (um2 & f2));
+                if (first)
+                    ESTAMP(EP_CLAIM);
                 if (!cm)
                     break;
-                if (round >= POM_ENC_FWD) {
-                    end = (uint32_t)__builtin_ctzll(cm);   // the window ends at a path lane
+                const uint32_t c = (uint32_t)__builtin_ctzll(cm);   // never lane 0
+                if (fwd >= POM_ENC_FWD) {
+                    end = c;                             // the window ends at a path lane
                     break;
                 }
-                const uint32_t c = (uint32_t)__builtin_ctzll(cm);   // never lane 0
-                if (STAMPS)
-                    acc[EC_FWD] += 1;
                 resolved |= 1ull << c;
                 const uint64_t below_c = (1ull << c) - 1;
                 const uint64_t pm = path & below_c;      // exact path lanes below c
@@ -834,8 +860,14 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                 const bool u2c = ((um2 >> c) & 1ull) != 0;
                 const uint64_t wm1 = wave_ballot(slot == h1c) & pm;
                 const uint64_t wm2 = wave_ballot(slot == h2c) & pm & (u2c ? ~0ull : 0ull);
-                if (!wm1 && !wm2)                        // a claim-table alias: c was exact
-                    continue;                            // (claims again)
+                if (!wm1 && !wm2) {                      // a false alarm: c was exact
+                    if (STAMPS)
+                        acc[EC_FALSE] += 1;
+                    continue;
+                }
+                fwd++;
+                if (STAMPS)
+                    acc[EC_FWD] += 1;
                 const bool via2 = wm1 == 0;              // h1 unchanged, its test failed again: h2
                 const uint32_t j = 63u - (uint32_t)__builtin_clzll(via2 ? wm2 : wm1);
                 superseded |= 1ull << j;                 // c writes j's slot after j
@@ -868,7 +900,7 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
             if (!FUSED || end != end0)
                 load_at<kCmpW, POM_PW_AUX>(B, ip + end + l, npw);
 
-            ESTAMP(EP_CLAIM);
+            ESTAMP(EP_FWDR);
             // ---- tokens for the matches before the cut ------------------------
             // Each match lane writes its own token: its literal run starts
             // after the highest lane below it that is not a literal path lane
@@ -1128,6 +1160,10 @@ __device__ __forceinline__ void gdict1_body(
         E.prio = !dyn;                               // (block tickets: mixed sizes, no priority)
         uint64_t acc[EP_N] = {};
         parse_wave<STAMPS, true, true>(S, D, in, n, l, acc, &E);
+        if (STAMPS) {                                // (s_getreg_b32 of HW_REG_HW_ID and HW_REG_XCC_ID, all 32 bits)
+            acc[EC_HWID] = __builtin_amdgcn_s_getreg(4 | (31 << 11));
+            acc[EC_XCC] = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+        }
         if (STAMPS && l == 0)
             for (int i = 0; i < EP_N; i++)
                 stamps[(size_t)b * kEncStampSlots + i] = acc[i];
@@ -1246,7 +1282,7 @@ extern "C" int lzo_mi355x_launch_compress_fast(const uint8_t* src, const uint64_
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// Diagnostic: the same encoder with parse-wave phase stamps (16 x u64 per block).
+// Diagnostic: the same encoder with parse-wave phase stamps (24 x u64 per block).
 extern "C" int lzo_mi355x_debug_compress_fast_stamps(const uint8_t* src, const uint64_t* src_off,
                                                      const uint32_t* src_len, uint8_t* dst,
                                                      const uint64_t* dst_off,
@@ -1281,7 +1317,7 @@ extern "C" int lzo_mi355x_debug_compress_gdict_stamps(const uint8_t* src, const 
 }
 
 // Diagnostic: the one-wave global-dictionary encoder (the bench's) with
-// parse-wave phase stamps (16 x u64 per block; no start order).
+// parse-wave phase stamps (24 x u64 per block; no start order).
 extern "C" int lzo_mi355x_debug_compress_gdict1_stamps(const uint8_t* src, const uint64_t* src_off,
                                                        const uint32_t* src_len, uint8_t* dst,
                                                        const uint64_t* dst_off,

@@ -28,7 +28,7 @@ zo = np.zeros(nb, dtype=np.uint64); zo[1:] = np.cumsum((caps[:-1] + 255) // 256 
 za = torch.zeros(int(zo[-1] + caps[-1]) + 256, dtype=torch.uint8, device=dev)
 zb = lzo.DeviceBatch(za, t(zo.view(np.int64)), t(caps.astype(np.uint32).view(np.int32)))
 zl = torch.zeros(nb, dtype=torch.int32, device=dev); zs = torch.zeros_like(zl)
-SLOTS = 16
+SLOTS = 24                                 # (kEncStampSlots)
 stamps = torch.zeros(nb * SLOTS, dtype=torch.int64, device=dev)
 fn = getattr(lib, "lzo_mi355x_debug_compress_fast_stamps", None)
 if fn is not None:
@@ -82,8 +82,25 @@ if fn is None or a.nostamps:
     sys.exit(0)
 phases = ["setup", "probe", "cand", "path", "claim", "tok", "dict", "pushwait"]
 counts = ["windows", "extend", "tokens", "pathit", "extit", "end_cross", "end_cap", "fwd"]
+# (slots 16..19: the forwarding rounds' cycles -- "claim" is the claim reads up
+# to the first conflict mask --, false alarms, and the HW_ID and XCC_ID registers)
+FWDR, FALSE, HWID, XCC = 16, 17, 18, 19
 for name, t_ in (("lds", stamps), ("gdict", gstamps), ("gdict1", g1stamps)):
     st = t_.view(nb, SLOTS).double().cpu().numpy()
-    print(name, "parse cycles/block (mean):", {n: int(st[:, i].mean()) for i, n in enumerate(phases)},
-          "total", int(st[:, :len(phases)].sum(1).mean()))
-    print(name, "counts/block (mean):", {n: round(float(st[:, len(phases) + i].mean()), 1) for i, n in enumerate(counts)})
+    cyc = {n: int(st[:, i].mean()) for i, n in enumerate(phases)}
+    cyc["fwdrounds"] = int(st[:, FWDR].mean())
+    total = sum(cyc.values())
+    print(name, "parse cycles/block (mean):", cyc, "total", total)
+    print(name, "share of the chain (%):", {n: round(100.0 * v / max(total, 1), 1) for n, v in cyc.items()})
+    cnt = {n: round(float(st[:, len(phases) + i].mean()), 1) for i, n in enumerate(counts)}
+    cnt["false_alarm"] = round(float(st[:, FALSE].mean()), 1)
+    print(name, "counts/block (mean):", cnt)
+# Where the one-wave kernel's blocks ran: HW_ID has cu_id in bits 11:8, sh_id in
+# bit 12 and se_id in bits 15:13; XCC_ID has the XCD in bits 3:0.
+raw = g1stamps.view(nb, SLOTS).cpu().numpy()
+hw, xcc = raw[:, HWID], raw[:, XCC] & 0xF
+cu = (xcc << 8) | (((hw >> 13) & 7) << 5) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xF)
+per_cu = np.bincount(np.unique(cu, return_inverse=True)[1])
+print(f"gdict1 blocks per CU: {len(per_cu)} CUs used, histogram (blocks: CUs)",
+      {int(k): int(v) for k, v in zip(*np.unique(per_cu, return_counts=True))})
+print("gdict1 blocks per XCD:", {int(k): int(v) for k, v in zip(*np.unique(xcc, return_counts=True))})

@@ -29,7 +29,9 @@ for rel in ("trace/bench_kernel_stats.csv", "trace/bench_agent_info.csv"):
     p = os.path.join(src, rel)
     if os.path.exists(p):
         shutil.copy(p, os.path.join(dst, os.path.basename(p)))
-shutil.copy(os.path.join(src, "bench_traced.log"), os.path.join(dst, "bench_traced.log"))
+# (the bench's own output; the profiler's notes on the files it opened stay behind)
+with open(os.path.join(src, "bench_traced.log")) as f, open(os.path.join(dst, "bench_traced.log"), "w") as g:
+    g.writelines(line for line in f if "Opened result file" not in line)
 
 stats = {r["Name"]: r for r in csv.DictReader(open(os.path.join(src, "trace/bench_kernel_stats.csv")))}
 trace = list(csv.DictReader(open(os.path.join(src, "trace/bench_kernel_trace.csv"))))
