@@ -4,7 +4,7 @@
 // compressed input as a pipeline:
 //
 //  * PARSER wave (wave 1) finds the instructions of piece q+1.. while the
-//    executor runs piece q, and is also the block's only HBM writer.
+//    executor runs piece q; it only parses and issues no output stores.
 //    Parse (lane = kSeg-byte input segment): the LZO1X grammar
 //    (lib/minilzo.c:3308-3699) is a state machine
 //    over instruction starts (pos, state), state A (top), B (after a literal
@@ -21,15 +21,12 @@
 //    exactly only where a guess was wrong.  One more walk per lane writes the
 //    ops (length, source) of the true path to one of kSlots per-block op slots
 //    in global scratch.
-//    Writer duty, between parse steps: copy final output from the LDS ring to
-//    HBM in 1-KiB dwordx4 chunks; publish `issued` (ring slots reusable) at
-//    once and `landed` (readable from HBM) when the executor needs it.
 //
-//  * EXECUTOR wave (wave 0) issues no stores, so its loads never queue behind
-//    stores (gfx9 vmcnt retires a wave's loads and stores in one in-order
-//    queue).  Per 64 ops of a published piece: a DPP prefix sum gives output
-//    offsets; literal spans and far match sources are copied into an LDS
-//    source buffer with one batched load round trip; source forwarding and
+//  * EXECUTOR wave (wave 0) produces the output and stores it.  Per window of
+//    64 ops of a published piece: a DPP prefix sum gives output offsets;
+//    literal spans and far match sources are copied into an LDS source buffer
+//    with one batched load round trip; source forwarding lets a match read
+//    the source of the earlier op it copies from; the window is then cut into
 //    batches whose match sources all precede the batch.  Every batch is
 //    produced 1 KiB per step into the LDS output ring: a lane is a 16-byte
 //    chunk of one op (op starts tagged per chunk, a ballot maps every chunk to
@@ -40,6 +37,10 @@
 //        (the wrapped part read p bytes lower) merged by a byte mask;
 //      - a match of period 1..15: its pattern, expanded by v_perm with a
 //        selector table indexed by (period, phase).
+//    Final ring bytes go to HBM from this wave in whole 1-KiB pieces (one
+//    dwordx4 store per lane), trailing production by POM_STORE_LAG; a source
+//    older than the ring is read back from HBM after a vmcnt(0) for the
+//    stores that wrote it.
 //
 // Anything the fast path does not handle exactly (malformed input, lookbehind
 // or capacity errors, op-list overflow, EOF not at the end, misaligned
@@ -50,6 +51,7 @@
 #include <stdint.h>
 
 #include "lzo_mi355x_kernels.h"
+#include "lzo1x_wave.h"
 
 namespace {
 
@@ -76,9 +78,9 @@ static_assert(kOpMax < (1u << 16), "piece info: 16-bit op count");
 #endif
 constexpr uint32_t kSlots = POM_SLOTS;           // parsed pieces the parser may run ahead
 static_assert((kSlots & (kSlots - 1)) == 0, "slots: power of two");
-#ifndef POM_WRITER_SLEEP
-#define POM_WRITER_SLEEP 127                     // idle writer sleeps ~8K cycles between polls
-#endif
+// A parser kSlots pieces ahead of its executor sleeps ~8K cycles between polls
+// of `consumed` (s_sleep units of 64 cycles): the executor needs the issue slots.
+constexpr int kSlotWaitSleep = 127;
 #ifndef POM_FWD_ROUNDS
 #define POM_FWD_ROUNDS 3                         // source-forwarding rounds per window
 #endif
@@ -88,26 +90,14 @@ static_assert((kSlots & (kSlots - 1)) == 0, "slots: power of two");
 #ifndef POM_RING
 #define POM_RING 4096
 #endif
-#ifndef POM_PRIO
-#define POM_PRIO 1                               // final-round blocks: parser at priority 3, executor 3..0 by bytes left
-#endif
 #ifndef POM_PRIO_STEP
 #define POM_PRIO_STEP 10240                      // executor priority drops every this many bytes left
 #endif
 #ifndef POM_PARSER_PRIO
-#define POM_PARSER_PRIO 1                        // final-round parser wave priority (3 while it was also the writer)
-#endif
-#ifndef POM_LAZY_PUB
-#define POM_LAZY_PUB 1                           // hand output to the writer per completed 1-KiB chunk
+#define POM_PARSER_PRIO 1                        // final-round parser wave priority (the executor: 3..0 by bytes left)
 #endif
 #ifndef POM_EXEC_SLEEP
-#define POM_EXEC_SLEEP 16                        // executor waits sleep ~1K cycles between polls
-#endif
-#ifndef POM_DUTY_EVERY
-#define POM_DUTY_EVERY 4                         // parser pass-1 iterations between writer duties
-#endif
-#ifndef POM_EXEC_STORES
-#define POM_EXEC_STORES 1                        // the executor stores its own output (the parser only parses)
+#define POM_EXEC_SLEEP 16                        // waits on the other wave sleep ~1K cycles between polls
 #endif
 #ifndef POM_STORE_LAG
 #define POM_STORE_LAG 2048                       // executor stores trail its production by this much
@@ -130,7 +120,10 @@ constexpr uint32_t kInfoErr = 1u << 17;          // piece info: the block needs 
 // A step covers at most 64 chunks of 16 bytes: an op read by a step whose
 // first byte is xs lies at most kStepSpan bytes after xs.
 constexpr uint32_t kStepSpan = 16 * kWave + 16;
-// (diagnostics: why, in bits 20..23 of the piece info / the CN_REASON stamp)
+// (diagnostics: why, in bits 20..23 of the piece info / the CN_REASON stamp.
+// The numbers are an interface -- scripts/diag_decode.py and recorded profiles
+// name them by index.  RS_SPACE, RS_LANDED and RS_WRITER are retired: they
+// were waits on the parser-as-writer and no longer occur.)
 enum { RS_NONE, RS_OFF_END, RS_BAD, RS_OPS, RS_DEAD, RS_EWAIT, RS_OVERRUN, RS_LOOKBEHIND,
        RS_SPACE, RS_LANDED, RS_HEAD, RS_WRITER, RS_POOL };
 
@@ -163,11 +156,8 @@ struct __attribute__((aligned(16))) FastLds {
     // parser
     uint32_t stage[kStageBytes / 4];
     // hand-off words (LDS, workgroup scope)
-    uint32_t produced;        // executor -> writer: output bytes final in the ring
-    uint32_t issued;          // writer -> executor: stores issued (ring slots reusable)
-    uint32_t landed;          // writer -> executor: output bytes stored to HBM and landed
-    uint32_t need;            // executor -> writer: landed position it waits for
-    uint32_t state;           // executor -> parser: 0 running, 1 finished, 2 refused
+    uint32_t produced;        // executor: the block's output length, set when it finishes
+    uint32_t state;           // executor -> parser: 0 running, 1 finished (output stored), 2 refused
     uint32_t parsed;          // parser -> executor: pieces whose ops are in their slot
     uint32_t consumed;        // executor -> parser: pieces whose slot is free again
     uint32_t pinfo[kSlots];   // per slot: op count | kInfoEof | kInfoErr
@@ -189,29 +179,9 @@ static_assert(offsetof(FastLds, psel) % 16 == 0 && offsetof(FastLds, stage) % 16
 static_assert(sizeof(FastLds) * 2 * POM_WAVES_PER_EU <= 160 * 1024, "LDS budget");
 
 
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __ballot(p); }
 __device__ __forceinline__ void wave_order() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
-// Lane masks straight from a v_cmp (a ballot of a compound bool costs a
-// v_cndmask and a v_cmp more): active lanes with a < b, a >= b, (int)a >= 0.
-__device__ __forceinline__ uint64_t mask_lt(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 36); }
-__device__ __forceinline__ uint64_t mask_ge(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 35); }
+// (as the lane masks of lzo1x_wave.h) active lanes with (int)a >= 0
 __device__ __forceinline__ uint64_t mask_nonneg(uint32_t a) { return __builtin_amdgcn_sicmp((int32_t)a, 0, 39); }
-
-// Inclusive prefix sum over the wave: DPP row shifts inside each 16-lane row,
-// then the row totals via readlane (no LDS round trip).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
-    const uint32_t r0 = lane_read(v, 15), r1 = lane_read(v, 31), r2 = lane_read(v, 47);
-    const uint32_t row = lane_id() >> 4;
-    v += (row >= 1 ? r0 : 0u) + (row >= 2 ? r1 : 0u) + (row >= 3 ? r2 : 0u);
-    return v;
-}
 
 // (diagnostics only) maximum over the wave
 __device__ __forceinline__ uint32_t wave_max_dbg(uint32_t v)
@@ -230,23 +200,15 @@ __device__ __forceinline__ uint32_t shift_up1(uint32_t v, uint32_t fill)
     return lane_id() == 0 ? fill : u;
 }
 
-__device__ __forceinline__ uint32_t lds_load(const uint32_t* p)
-{
-    return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_store(uint32_t* p, uint32_t v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 // Drain of the last round of blocks.  Arbitration by age lets the oldest
 // waves of a CU run ahead; the blocks then finish one by one and the last few
 // waves cannot fill their SIMDs.  In the final round (blockIdx >= prio_from)
 // the executor's priority follows the output bytes it has left: 3 while 3 steps
 // (POM_PRIO_STEP) or more remain, then 2, 1 and 0 below one step, so blocks
 // that are behind win issue over those ahead and a CU's blocks finish
-// together.  The parser wave (also the block's HBM writer) stays at 3 so that
-// it keeps ahead of its executor.  Earlier rounds keep the default priority:
+// together.  The parser wave runs at POM_PARSER_PRIO (1): it only parses, and
+// stays ahead of its executor without the top priority.  Earlier rounds keep
+// the default priority:
 // with blocks queued behind them, finishing early is what frees a slot.
 __device__ __forceinline__ void prio_by_bytes_left(uint32_t left)
 {
@@ -479,9 +441,6 @@ __device__ __forceinline__ Step decode_step(const FastLds& s, const Blk& k, uint
 // decode runs on the scalar unit -- a few SALU per field instead of a VALU
 // instruction for all 64 lanes (~55 per instruction decoded).  Same fields as
 // decode_step; the rare instructions take decode_one (per lane, all alike).
-#ifndef POM_UWALK
-#define POM_UWALK 1
-#endif
 __device__ __forceinline__ Step decode_step_u(const FastLds& s, const Blk& k, uint32_t pos, uint32_t st)
 {
     const uint32_t rel = pos - k.P;
@@ -623,16 +582,8 @@ __device__ __forceinline__ void lds_write1(uint32_t a, uint32_t v)
 
 // The first len (<= 16) bytes of v at LDS address a: one b128 for a whole
 // chunk, else b64/b32/b16/b8 pieces.
-__device__ __forceinline__ __attribute__((unused)) void lds_write_part(uint32_t a, uint4 v, uint32_t len)
+__device__ __forceinline__ void lds_write_part(uint32_t a, uint4 v, uint32_t len)
 {
-#ifdef POM_BYTE_WRITES
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t i = 0; i < 16; i++)
-        if (i < len)
-            lds_write1(a + i, w[i >> 2] >> (8 * (i & 3)));
-    return;
-#endif
     if (len == 16u) {
         lds_write16(a, v);
         return;
@@ -658,59 +609,36 @@ __device__ __forceinline__ __attribute__((unused)) void lds_write_part(uint32_t 
         lds_write1(ad, w0);
 }
 
-typedef __attribute__((address_space(1))) const uint32_t gdword;
-
 // 4 bytes at an arbitrary global address via two aligned dword loads (an
-// aligned dword that overlaps valid bytes never leaves their page).  NT: L2
-// served (the vector L1 is not coherent with the writer wave's stores).
+// aligned dword that overlaps valid bytes never leaves their page).
 // Address-space-1 pointers keep these global_load (vmcnt only), not flat_load
 // (which also waits on lgkmcnt and so on every outstanding LDS access).
-#ifndef POM_OUT_NT
-#define POM_OUT_NT 0                             // writer: non-temporal output stores
-#endif
-#ifndef POM_SRC_SC1
-#define POM_SRC_SC1 1                            // source-buffer loads: agent-scope (L2-allocating) instead of non-temporal
-#endif
-#ifndef POM_FAR_SC1
-#define POM_FAR_SC1 1                            // far reads: agent-scope (L2-allocating) loads instead of non-temporal
-#endif
-#ifndef POM_WRAP_MIRROR
-#define POM_WRAP_MIRROR 1                        // a ring-wrapping chunk: one write through the mirror, then a 16-byte copy
-#endif
-#ifndef POM_FAR_UNCOND
-#define POM_FAR_UNCOND 1                         // far reads: all five loads unconditional (clamped addresses)
-#endif
-template <bool NT>
 __device__ __forceinline__ uint32_t global_dword(const uint8_t* p)
 {
     const uintptr_t a = (uintptr_t)p;
     gdword* q = (gdword*)(a & ~(uintptr_t)3);
     const uint32_t sh = (uint32_t)(a & 3);
-    uint32_t w0, w1 = 0;
-    if (NT) {
-        w0 = __builtin_nontemporal_load(q);
-        if (sh)
-            w1 = __builtin_nontemporal_load(q + 1);
-    } else {
-        w0 = q[0];
-        if (sh)
-            w1 = q[1];
-    }
+    const uint32_t w0 = q[0];
+    uint32_t w1 = 0;
+    if (sh)
+        w1 = q[1];
     return sh ? funnel(w0, w1, sh) : w0;
 }
 
-// Bytes [lo, hi) (hi <= 16) of the 16 at global address p, read through L2
-// with aligned dword loads that each hold at least one of those bytes (so no
-// load leaves their pages); the other bytes read as 0.
+// Bytes [lo, hi) (lo < hi <= 16) of the 16 at global address p, read through
+// L2 with agent-scope loads (never a stale vector-L1 line); the other bytes
+// read as 0.  For lo < hi every load is of an aligned dword that holds at
+// least one of those bytes, so none leaves their pages.  lo < hi is the
+// callers' business: it is not checked here, and with hi <= lo dwords beyond
+// the span are loaded.
 __device__ __forceinline__ uint4 global_read16(const uint8_t* p, uint32_t lo, uint32_t hi)
 {
     const uintptr_t a = (uintptr_t)p;
     gdword* q = (gdword*)(a & ~(uintptr_t)3);
     const uint32_t sh = (uint32_t)(a & 3);
     uint32_t w[5];
-#if POM_FAR_UNCOND
-    // every load issued (no exec branch per dword): a dword outside
-    // [i0, i1] reads dword i0 or i1 again and is then dropped
+    // all five loads are written unconditionally: a dword outside [i0, i1]
+    // reads dword i0 or i1 again and is then dropped
     const uint32_t i0 = (lo + sh) >> 2, i1 = (hi + sh - 1) >> 2;
 #pragma unroll
     for (uint32_t i = 0; i < 5; i++) {
@@ -718,15 +646,6 @@ __device__ __forceinline__ uint4 global_read16(const uint8_t* p, uint32_t lo, ui
         const uint32_t v = __hip_atomic_load((uint32_t*)(q + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         w[i] = i == j ? v : 0u;
     }
-#else
-#pragma unroll
-    for (uint32_t i = 0; i < 5; i++) {
-        // aligned dword i holds bytes 4i - sh .. 4i + 3 - sh of the span
-        const bool use = 4 * i < hi + sh && 4 * i + 4 > lo + sh;
-        w[i] = use ? (POM_FAR_SC1 ? __hip_atomic_load((uint32_t*)(q + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                  : __builtin_nontemporal_load(q + i)) : 0u;
-    }
-#endif
     uint4 v;
     v.x = __builtin_amdgcn_alignbyte(w[1], w[0], sh);
     v.y = __builtin_amdgcn_alignbyte(w[2], w[1], sh);
@@ -785,7 +704,7 @@ __device__ __forceinline__ WalkRes walk_true(const FastLds& S, const Blk& k, uin
             }
         }
         bool slow = false;
-        const Step r = (!SPEC && POM_UWALK) ? decode_step_u(S, k, pos, st) : decode_step<SPEC>(S, k, pos, st, &slow);
+        const Step r = SPEC ? decode_step<true>(S, k, pos, st, &slow) : decode_step_u(S, k, pos, st);
         if (SPEC && slow) {
             w.fl = FL_UNK;
             break;
@@ -812,7 +731,8 @@ __device__ __forceinline__ WalkRes walk_true(const FastLds& S, const Blk& k, uin
 // Diagnostic build only (STAMPS): per-phase s_memtime cycle sums and event
 // counts go to stamps[b * kStampSlots + i]; no output value depends on them.
 // Each wave writes only the slots it owns (parser: parser_slot).
-// scripts/diag_decode.py knows this order.
+// scripts/diag_decode.py knows this order, and recorded profiles hold it: the
+// indices stay.  PH_PDUTY (the parser's writer duty) is retired and stays 0.
 enum { PH_STAGE, PH_PASS1, PH_PWALK, PH_MERGE, PH_COUNT, PH_WRITE, PH_PSLOT, PH_PDUTY,
        PH_EWAIT, PH_WLOAD, PH_WSCAN, PH_FARI, PH_FWD, PH_FARC, PH_BATCH,
        PH_SPACE, PH_FLAGS, PH_GATHER, PH_PUB,
@@ -836,64 +756,9 @@ __device__ __forceinline__ bool parser_slot(int i)
         }                                                           \
     } while (0)
 
-// ---------------------------------------------------------------------------
-// Writer duty (parser wave, between parse steps): final ring bytes go to HBM
-// in 1-KiB chunks, one dwordx4 store per lane.  Two positions are published:
-//   issued  -- stores issued (their data left the ring): those ring slots
-//              may be overwritten;
-//   landed  -- stores known to be in HBM: that output may be read back.
-// `landed` trails by one batch of chunks: the wait for a batch is taken when
-// the next one is issued (by then it has long landed), or at once when the
-// executor asks for more (S.need) -- so the executor never waits on a store
-// it does not read.
-// Returns 2 once the executor refused the block, 1 once everything it
-// produced has landed after it finished, 0 otherwise.
-// ---------------------------------------------------------------------------
 constexpr uint32_t kChunk = 16 * kWave;          // 1 KiB per store instruction
 
-struct WState {
-    uint32_t issued;        // output bytes whose stores were issued
-    uint32_t landed;        // output bytes published as landed
-};
-
-__device__ __forceinline__ uint32_t writer_duty(FastLds& S, uint8_t* out, uint32_t l, WState& w)
-{
-    if (POM_EXEC_STORES)
-        return 0;                                      // (the executor stores its own output)
-    const uint32_t state = lds_load(&S.state);
-    const uint32_t prod = lds_load(&S.produced);
-    if (state == 2)
-        return 2;                                      // refused: the exact decoder redoes it
-    const uint32_t upto = state == 1 ? prod : (prod & ~(kChunk - 1));
-    const bool fresh = upto > w.issued;
-    if (w.landed < w.issued && (fresh || state == 1 || lds_load(&S.need) > w.landed)) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): the last batch landed
-        w.landed = w.issued;
-        lds_store(&S.landed, w.landed);
-    }
-    if (!fresh)
-        return (state == 1 && w.landed == prod) ? 1u : 0u;
-    for (int c = 0; c < 4 && w.issued < upto; c++) {
-        const uint32_t end = upto - w.issued > kChunk ? w.issued + kChunk : upto;
-        const uint32_t x = w.issued + 16 * l;
-        if (x + 16 <= end) {
-            const uint32_t i = x & kRingMask;
-            const uint4 v = *(const uint4*)&S.ring[i >> 2];
-            if (POM_OUT_NT)
-                __builtin_nontemporal_store((v4u32){v.x, v.y, v.z, v.w}, (v4u32*)(out + x));
-            else
-                *(uint4*)(out + x) = v;
-        } else if (x < end) {
-            for (uint32_t q = 0; x + q < end; q++)
-                out[x + q] = (uint8_t)ring_byte(S, x + q);
-        }
-        w.issued = end;
-    }
-    lds_store(&S.issued, w.issued);                    // (after the ring reads completed)
-    return 0;
-}
-
-// Executor-side stores (POM_EXEC_STORES): the executor stores ring bytes
+// Output stores: the executor stores ring bytes
 // [at, end) of its own output, one dwordx4 per lane for whole 16-byte pieces
 // (bytes past `end` are not written).  Its LDS reads of the ring come before
 // any later ring write of the wave (LDS accesses of a wave complete in order),
@@ -919,16 +784,13 @@ __device__ __forceinline__ void exec_store(const FastLds& S, uint8_t* out, uint3
 
 // ---------------------------------------------------------------------------
 // Parser wave: pieces in stream order with exact entries (the true exit of
-// the previous piece), ops to slot q mod kSlots; writer duty in between.
+// the previous piece), ops to slot q mod kSlots.
 // ---------------------------------------------------------------------------
 template <bool STAMPS>
 __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict__ gops, uint32_t l,
                                             uint64_t* acc)
 {
     uint64_t tmark = STAMPS ? __builtin_amdgcn_s_memtime() : 0;
-    WState w;
-    w.issued = 0;
-    w.landed = 0;
     uint32_t entry_pos = 0, entry_st = ST_F;   // true entry of the current piece
     for (uint32_t q = 0;; q++) {
         // Skip pieces in which no instruction starts (inside a long literal run).
@@ -936,10 +798,9 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
             k.P = entry_pos - (entry_pos % kPiece);
         // a free slot: the executor is done with piece q - kSlots
         for (uint32_t spin = 0; q - lds_load(&S.consumed) >= kSlots; spin++) {
-            if (writer_duty(S, k.out, l, w) == 2 || spin > (1u << 22) ||
-                (POM_EXEC_STORES && lds_load(&S.state) == 2))
+            if (spin > (1u << 22) || lds_load(&S.state) == 2)
                 return;                        // the executor refused (or is stuck)
-            __builtin_amdgcn_s_sleep(POM_WRITER_SLEEP);
+            __builtin_amdgcn_s_sleep(kSlotWaitSleep);
         }
         STAMP(PH_PSLOT);
         if (STAMPS)
@@ -958,7 +819,7 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
             for (uint32_t i = l * 4; i < kStageBytes; i += kWave * 4) {
                 uint32_t v = 0;
                 if (i + 4 <= k.staged)
-                    v = global_dword<false>(base + i);
+                    v = global_dword(base + i);
                 else
                     for (uint32_t j = i; j < k.staged; j++)
                         v |= (uint32_t)base[j] << (8 * (j - i));
@@ -978,7 +839,7 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
             Marks M;
             M.m[0] = M.m[1] = M.m[2] = M.m[3] = 0;
             M.two = 0;
-            for (uint32_t it = 1;; it++) {
+            for (;;) {
                 const bool act = p1 && pos < c1 && pos < k.z;
                 if (!wave_ballot(act))
                     break;
@@ -1006,12 +867,6 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
                 }
                 if (STAMPS)
                     acc[CN_IT_PASS1] += 1;
-                if (it % POM_DUTY_EVERY == 0) {
-                    STAMP(PH_PASS1);
-                    if (writer_duty(S, k.out, l, w) == 2)
-                        return;
-                    STAMP(PH_PDUTY);
-                }
             }
             M.xpos = !p1 ? entry_pos : pos >= k.z ? kPosEnd : pos;
             M.xst = !p1 ? entry_st : st;
@@ -1023,9 +878,6 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
             const uint32_t apos = shift_up1(M.xpos, entry_pos), ast = shift_up1(M.xst, entry_st);
             const WalkRes f = walk_true<true>(S, k, c0, c1, M, apos, ast);
             STAMP(PH_PWALK);
-            if (writer_duty(S, k.out, l, w) == 2)
-                return;
-            STAMP(PH_PDUTY);
             // Where lane i's true entry E equals its assumed one and its walk
             // finished, lanes i, i+1, ... stay right as long as each walk ended
             // at the next lane's assumed entry (f_l == x_l, FL_OK) and that
@@ -1034,18 +886,11 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
             uint32_t epos = kPosEnd, est = ST_A, ecnt = 0;
             uint64_t run = 0;                          // lanes whose parallel walk is true
             bool dead = false;
-#ifdef POM_DEBUG_DEAD
-            bool dbg_stage_bad = false;
-#endif
             {
                 const uint64_t brk = wave_ballot(f.fl != FL_OK || f.pos != M.xpos || f.st != M.xst) << 1;
                 const uint64_t unk = wave_ballot(f.fl == FL_UNK);
                 uint32_t E = entry_pos, Est = entry_st;
                 uint32_t i = 0;
-#ifdef POM_DEBUG_DEAD
-                uint32_t dbg_i = 99, dbg_E = 0, dbg_Est = 0;
-                (void)dbg_i; (void)dbg_E; (void)dbg_Est;
-#endif
                 while (i < (uint32_t)kWave) {
                     const uint32_t ci1 = k.P + (i + 1) * kSeg;
                     if (E >= ci1) {                    // no true start in segment i
@@ -1066,9 +911,6 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
                         }
                         if (fl == FL_DEAD) {
                             dead = true;
-#ifdef POM_DEBUG_DEAD
-                            dbg_i = 100 + qq - 1;
-#endif
                             break;
                         }
                         i = qq;
@@ -1083,10 +925,6 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
                     Mi.two = lane_read(M.two, i);
                     Mi.xpos = lane_read(M.xpos, i);
                     Mi.xst = lane_read(M.xst, i);
-#ifdef POM_DEBUG_DEAD
-                    dbg_E = E;
-                    dbg_Est = Est;
-#endif
                     const WalkRes g = walk_true<false>(S, k, ci1 - kSeg, ci1, Mi, E, Est);
                     if (STAMPS)
                         acc[CN_WALKS] += 1;
@@ -1098,40 +936,18 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
                     E = g.pos;
                     Est = g.st;
                     STAMP(PH_MERGE);
-                    if (writer_duty(S, k.out, l, w) == 2)
-                        return;
-                    STAMP(PH_PDUTY);
                     if (g.fl == FL_EOF) {
                         eof = true;
                         break;
                     }
                     if (g.fl == FL_DEAD) {
                         dead = true;
-#ifdef POM_DEBUG_DEAD
-                        dbg_i = i;
-#endif
                         break;
                     }
                     i++;
                 }
                 next_pos = E;                          // (uniform: the piece's true exit)
                 next_st = Est;
-#ifdef POM_DEBUG_DEAD
-                if (dead || (!eof && E == kPosEnd)) {
-                    // (diagnostic) does the LDS stage still hold the input?
-                    bool diff = false;
-                    for (uint32_t i = l * 4; i < kStageBytes; i += kWave * 4) {
-                        uint32_t v = 0;
-                        if (i + 4 <= k.staged)
-                            v = global_dword<false>(k.in + k.P + i);
-                        else
-                            for (uint32_t j = i; j < k.staged; j++)
-                                v |= (uint32_t)k.in[k.P + j] << (8 * (j - i));
-                        diff |= S.stage[i >> 2] != v;
-                    }
-                    dbg_stage_bad = wave_ballot(diff) != 0;
-                }
-#endif
                 if ((run >> l) & 1) {
                     epos = apos;
                     est = ast;
@@ -1144,10 +960,6 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
             if (dead) {
                 err = true;
                 reason = RS_DEAD;
-#ifdef POM_DEBUG_DEAD
-                if (dbg_stage_bad)
-                    reason = 12;                       // (diagnostic) the stage was overwritten
-#endif
             } else if (total_ops > kOpMax) {
                 err = true;
                 reason = RS_OPS;
@@ -1202,15 +1014,6 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
         entry_pos = next_pos;                          // next piece: the true exit
         entry_st = next_st;
         k.P += kPiece;
-        if (writer_duty(S, k.out, l, w) == 2)
-            return;
-        STAMP(PH_PDUTY);
-    }
-    // parse finished: writer only (with executor-side stores: nothing left)
-    for (uint32_t spin = 0; !POM_EXEC_STORES && spin < (1u << 22); spin++) {
-        if (writer_duty(S, k.out, l, w) != 0)
-            break;
-        __builtin_amdgcn_s_sleep(POM_WRITER_SLEEP);
     }
     STAMP(PH_PSLOT);
 }
@@ -1225,36 +1028,16 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
 // through linear addresses from kLinHbm (input position + kLinHbm).
 //
 // Where output bytes are (carry = output before this window): the ring holds
-// every position >= carry - kRing, and the executor waited for `landed` >=
-// carry - kRing, so every position below `landed` is in HBM.  Sources lie
-// below carry (db + span <= carry is required).
+// every position >= carry - kRing, and the executor's stores of everything
+// below carry - kRing were issued before those ring slots were reused; before
+// a window reads below the ring it waits vmcnt(0), so every position below
+// `landed` is in HBM.  Sources lie below carry (db + span <= carry is
+// required).
 // Far ops are never forwarded (their sources lie below the window), so the
 // copy is issued before forwarding -- which then hands buffer sources on to
 // the ops that forward to them -- and only committed to LDS after it, so the
 // loads' latency hides under the forwarding rounds.
 // ---------------------------------------------------------------------------
-// Executor: waits until the writer published landed >= need (asking for it
-// through S.need).
-__device__ __forceinline__ uint32_t wait_landed(FastLds& S, uint32_t need, uint32_t seen,
-                                                bool& refuse)
-{
-    if (seen >= need)
-        return seen;
-    seen = lds_load(&S.landed);
-    if (seen >= need)
-        return seen;
-    lds_store(&S.need, need);
-    for (uint32_t spin = 0; seen < need; spin++) {
-        if (spin > (1u << 20)) {               // writer stuck: let the exact path redo it
-            refuse = true;
-            break;
-        }
-        __builtin_amdgcn_s_sleep(POM_EXEC_SLEEP);
-        seen = lds_load(&S.landed);
-    }
-    return seen;
-}
-
 struct SrcCopy {
     uint32_t v[4];          // this lane's buffer dwords 4l .. 4l+3 (first aligned dword)
     uint32_t v1[4];         // (the next aligned dword, for unaligned input)
@@ -1339,14 +1122,9 @@ __device__ __forceinline__ SrcCopy src_issue(FastLds& S, const Blk& k, uint32_t 
         const uintptr_t qb = in_src && qa + 4 <= in_last ? qa + 4 : qa;
         w0[i] = S.ring[(a & kRingMask) >> 2];
         w1[i] = 0;
-        if (hbm[i]) {
-#if POM_SRC_SC1
+        if (hbm[i]) {                                        // agent scope: L2 allocating
             w0[i] = __hip_atomic_load((uint32_t*)qa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             w1[i] = __hip_atomic_load((uint32_t*)qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-            w0[i] = __builtin_nontemporal_load((gdword*)qa);
-            w1[i] = __builtin_nontemporal_load((gdword*)qb);
-#endif
         }
     }
     // (funnels in src_commit: the loads' latency hides under forwarding)
@@ -1442,10 +1220,9 @@ __device__ void opset_return(const OpPool& P, uint32_t set)
 }
 
 // Lane 0 of each wave when it is done with block b.  The second wave out
-// publishes the block -- by then the executor has decided (state 1: finished,
-// 2: refused) and the writer has landed what it could -- and returns the op
-// set.  A writer that gave up (it polls for a bounded time) leaves bytes
-// unstored: that block goes to the exact decoder like any refusal.
+// publishes the block -- by then the executor has decided (state 1: finished
+// and every output store landed; 2: refused, the exact decoder redoes the
+// block) -- and returns the op set.
 __device__ void block_close(FastLds& S, uint32_t b, uint32_t* __restrict__ out_len,
                             int32_t* __restrict__ status, uint32_t* __restrict__ fallback,
                             uint32_t* __restrict__ fallback_ids, const OpPool& P)
@@ -1454,12 +1231,12 @@ __device__ void block_close(FastLds& S, uint32_t b, uint32_t* __restrict__ out_l
         return;                                    // the other wave closes the block
     const uint32_t st = lds_load(&S.state);
     const uint32_t prod = lds_load(&S.produced);
-    if (st == 1 && lds_load(&S.landed) == prod) {
+    if (st == 1) {
         out_len[b] = prod;
         status[b] = 0;
     } else {
         status[b] = kFallback;
-        out_len[b] = 0xFA110000u | (st == 2 ? lds_load(&S.why) : (uint32_t)RS_WRITER);  // (diagnostics)
+        out_len[b] = 0xFA110000u | lds_load(&S.why);   // (diagnostics: state 2, the executor's reason)
         const uint32_t at = atomicAdd(&fallback[0], 1u);
         fallback_ids[at] = b;
     }
@@ -1488,9 +1265,6 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (threadIdx.x == 0) {
         S.produced = 0;
-        S.issued = 0;
-        S.landed = 0;
-        S.need = 0;
         S.state = 0;
         S.parsed = 0;
         S.consumed = 0;
@@ -1527,7 +1301,7 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
     bool refuse = ((uintptr_t)k.out & 15) != 0 || k.z >= (1u << 24) || k.z == 0 || opset == kNoSet;
     uint32_t reason = opset == kNoSet ? (uint32_t)RS_POOL : refuse ? (uint32_t)RS_HEAD : (uint32_t)RS_NONE;
     if (wave == 1) {
-        if (POM_PRIO && last_round)
+        if (last_round)
             __builtin_amdgcn_s_setprio(POM_PARSER_PRIO);
         if (!refuse)
             parser_wave<STAMPS>(S, k, gops, l, acc);
@@ -1548,12 +1322,10 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
     const uint32_t psel0 = base + (uint32_t)offsetof(FastLds, psel);
     const uint32_t psel1 = psel0 + (uint32_t)sizeof(S.psel[0]);
     uint32_t carry = 0;                        // output produced so far
-    uint32_t issued_seen = 0, landed_seen = 0; // last `issued` / `landed` read
-    // (POM_EXEC_STORES) output bytes whose stores this wave issued; landed_seen
-    // is then the stored count at its last vmcnt(0)
-    uint32_t stored = 0;
+    // output bytes whose stores this wave issued, and that count at its last
+    // vmcnt(0): everything below landed_seen is in HBM
+    uint32_t stored = 0, landed_seen = 0;
     uint32_t tag = 0;                          // step counter for the chunk tags
-    uint32_t published = 0;                    // last `produced` handed to the writer
     uint32_t q = 0, w0 = 0, total_ops = 0;     // piece, window start, piece's op count
     bool have_piece = false, eofq = false;
     uint64_t pf = 0;                           // prefetched op record of the next window
@@ -1611,25 +1383,15 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                     Sv = (uint32_t)(r >> 32);
                 }
             }
-            // what the source copy does not find in the ring (below carry -
-            // kRing) it reads from HBM: that output must have landed
-            if (!POM_EXEC_STORES && carry > kRing)
-                landed_seen = wait_landed(S, carry - kRing, landed_seen, refuse);
-            if (refuse) {
-                reason = RS_LANDED;
-                break;
-            }
-            // prefetch the next window's op records of this piece (with
-            // executor-side stores: after the landed check below, whose
-            // vmcnt(0) would otherwise wait for it)
+            // the next window's op records of this piece are prefetched after
+            // the landed check below, whose vmcnt(0) would otherwise wait for
+            // them
             have_pf = w0 + kWave < total_ops;
             auto prefetch_records = [&]() {
                 if (have_pf && w0 + kWave + l < total_ops)
                     pf = __hip_atomic_load((const uint64_t*)(slot + w0 + kWave + l), __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT);
             };
-            if (!POM_EXEC_STORES)
-                prefetch_records();
             STAMP(PH_WLOAD);
             if (STAMPS)
                 acc[CN_WINDOWS] += 1;
@@ -1656,17 +1418,15 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
             const uint32_t ipos = Sv & ~kLitFlag;
             uint32_t db = lit ? kLitFlag | (kLinHbm + ipos) : o - Sv;
             uint32_t dp = (!lit && Sv < L) ? Sv : 0u;
-            if (POM_EXEC_STORES) {
-                // sources older than the ring are read back from HBM: the
-                // stores of those bytes (issued before their slots were
-                // reused, so stored >= carry - kRing) must have completed
-                if (carry > kRing && landed_seen < carry - kRing &&
-                    wave_ballot(l < nwin && !lit && db < carry - kRing)) {
-                    __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0)
-                    landed_seen = stored;
-                }
-                prefetch_records();
+            // sources older than the ring are read back from HBM: the stores
+            // of those bytes (issued before their slots were reused, so
+            // stored >= carry - kRing) must have completed
+            if (carry > kRing && landed_seen < carry - kRing &&
+                wave_ballot(l < nwin && !lit && db < carry - kRing)) {
+                __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0)
+                landed_seen = stored;
             }
+            prefetch_records();
             STAMP(PH_WSCAN);
             const SrcCopy fc = src_issue(S, k, l, nwin, carry, landed_seen, o, L, dp, lit, ipos, db);
             STAMP(PH_FARI);
@@ -1765,41 +1525,19 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                     const uint32_t x = op.x + k16;
                     const uint32_t rem = op.w - k16;
                     const uint32_t len = live ? (rem < 16u ? rem : 16u) : 0u;
-                    const uint32_t nl = c_end - C < (uint32_t)kWave ? c_end - C : (uint32_t)kWave;
                     const uint32_t xs = lane_read(x, 0);
-                    const uint32_t step_end = POM_EXEC_STORES ? 0u : lane_read(x + len, nl - 1);
                     STAMP(PH_FLAGS);
-                    // ring space: the stores of what the slots of [xs, step_end)
-                    // held must have been issued.  Executor-side stores: this
-                    // wave issues them itself, whole 1-KiB pieces of final
-                    // output (below xs), trailing its production by
-                    // POM_STORE_LAG so that a read back from HBM rarely waits
-                    // for a store still in flight.
-                    if (POM_EXEC_STORES) {
-                        const uint32_t want = xs > POM_STORE_LAG ? xs - POM_STORE_LAG : 0u;
-                        // (xs + kStepSpan bounds step_end without its readlane)
-                        while (stored + kChunk <= want || stored + kRing < (POM_EXEC_STORES ? xs + kStepSpan : step_end)) {
-                            exec_store_chunk(S, k.out, l, stored);
-                            stored += kChunk;
-                        }
+                    // ring space: the stores of what the slots this step
+                    // overwrites held must have been issued.  The step ends
+                    // below xs + kStepSpan, and this wave stores whole 1-KiB
+                    // pieces of final output (below xs), trailing its
+                    // production by POM_STORE_LAG so that a read back from HBM
+                    // rarely waits for a store still in flight.
+                    const uint32_t want = xs > POM_STORE_LAG ? xs - POM_STORE_LAG : 0u;
+                    while (stored + kChunk <= want || stored + kRing < xs + kStepSpan) {
+                        exec_store_chunk(S, k.out, l, stored);
+                        stored += kChunk;
                     }
-                    for (uint32_t spin = 0; !POM_EXEC_STORES && step_end > issued_seen + kRing; spin++) {
-                        if (spin > (1u << 20)) {       // writer stuck: let the exact path redo it
-                            refuse = true;
-                            reason = RS_SPACE;
-                            break;
-                        }
-                        if (spin) {
-                            if (spin == 1) {           // hand over what is final
-                                lds_store(&S.produced, xs);
-                                published = xs;
-                            }
-                            __builtin_amdgcn_s_sleep(POM_EXEC_SLEEP);
-                        }
-                        issued_seen = __builtin_amdgcn_readfirstlane(lds_load(&S.issued));
-                    }
-                    if (refuse)
-                        break;
                     STAMP(PH_SPACE);
                     if (STAMPS)
                         acc[CN_STEPS] += 1;
@@ -1849,19 +1587,15 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                                      sh);
                     }
                     if (mhbm) {
-                        if ((mhbm & mask_nonneg(op.y)) && xs + 16u > kRing) {  // (!lin: bit 31 clear)
-                            if (!POM_EXEC_STORES)
-                                landed_seen = wait_landed(S, xs + 16u - kRing, landed_seen, refuse);
-                            else if (landed_seen < xs + 16u - kRing) {
-                                // (stored >= step_end - kRing covers every byte read here:
-                                // sources below xs - kRing, 16 bytes from there)
-                                while (stored < xs + 16u - kRing) {
-                                    exec_store_chunk(S, k.out, l, stored);
-                                    stored += kChunk;
-                                }
-                                __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0)
-                                landed_seen = stored;
+                        // (!lin: bit 31 clear) output read back from HBM: sources
+                        // below xs - kRing, 16 bytes from there, stored and landed
+                        if ((mhbm & mask_nonneg(op.y)) && xs + 16u > kRing && landed_seen < xs + 16u - kRing) {
+                            while (stored < xs + 16u - kRing) {
+                                exec_store_chunk(S, k.out, l, stored);
+                                stored += kChunk;
                             }
+                            __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0)
+                            landed_seen = stored;
                         }
                         const uint8_t* gb = lin ? k.in - kLinHbm : k.out;
                         if (hA)
@@ -1869,8 +1603,6 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                         if (hB)                        // bytes n1.. of the span: from b on
                             vB = global_read16(gb + bb - n1, n1, len);
                     }
-                    if (refuse)
-                        break;
                     uint4 v = vA;
                     if (any_two) {
                         // bytes i < n1 from vA, the rest from vB
@@ -1897,7 +1629,6 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                     }
                     // ---- destination: the ring at x -----------------------------
                     const uint32_t xd = x & kRingMask;
-#if POM_WRAP_MIRROR
                     // a chunk that wraps the ring end runs on into the mirror
                     // of ring[0, 16); the ring's head is then copied back from
                     // the mirror (after every lane's mirror write: bytes other
@@ -1909,47 +1640,14 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                     }
                     if (mask_lt(kRing, xd + len) && l == 0)     // (len is 0 off the step)
                         lds_write16(base, lds_read16(base + kRing));
-#else
-                    const bool wcross = live && xd + len > kRing;
-                    if (live && !wcross) {
-                        lds_write_part(base + xd, v, len);
-                        if (xd < 16u)                  // keep the mirror of ring[0, 16)
-                            lds_write_part(base + kRing + xd, v, len);
-                    }
-                    if (mask_lt(kRing, xd + len)) {     // (wcross; len is 0 off the step)
-                        if (wcross) {                  // destination wraps the ring end
-                            const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-                            uint8_t* ldsw = (uint8_t*)&S;
-#pragma unroll
-                            for (uint32_t i = 0; i < 16; i++)
-                                if (i < len) {
-                                    const uint32_t y = (x + i) & kRingMask;
-                                    const uint8_t bv = (uint8_t)(wv[i >> 2] >> (8 * (i & 3)));
-                                    ldsw[y] = bv;
-                                    if (y < 16u)
-                                        ldsw[kRing + y] = bv;
-                                }
-                        }
-                    }
-#endif
                     wave_order();
                     STAMP(PH_GATHER);
-                    // bytes below step_end are final: hand them over once a
-                    // 1-KiB store chunk is complete (the writer stores whole chunks)
-                    if (!POM_EXEC_STORES && (!POM_LAZY_PUB || (step_end ^ published) >= kChunk)) {
-                        lds_store(&S.produced, step_end);
-                        published = step_end;
-                    }
-                    STAMP(PH_PUB);
+                    STAMP(PH_PUB);                     // (nothing to publish: this wave stores the bytes itself)
                 }
-                if (refuse)
-                    break;
                 s = e;
             }
-            if (refuse)
-                break;
             carry += wtotal;
-            if (POM_PRIO && last_round)
+            if (last_round)
                 prio_by_bytes_left(k.cap > carry ? k.cap - carry : 0u);
             wave_order();
         }
@@ -1962,7 +1660,7 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
         for (int i = 0; i < PH_N; i++)
             if (!parser_slot(i))
                 stamps[(size_t)b * kStampSlots + i] = acc[i];
-    if (POM_EXEC_STORES && !refuse) {
+    if (!refuse) {
         // the rest of the output, then wait for every store to land
         for (; stored < carry; stored += kChunk)
             exec_store(S, k.out, l, stored, carry - stored < kChunk ? carry : stored + kChunk);
@@ -1974,8 +1672,6 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
             lds_store(&S.why, reason);
             lds_store(&S.state, 2u);
         } else {
-            if (POM_EXEC_STORES)
-                lds_store(&S.landed, carry);                 // (block_close checks landed == produced)
             lds_store(&S.produced, carry);
             lds_store(&S.state, 1u);
         }

@@ -36,6 +36,7 @@
 
 #include "lzo_mi355x_kernels.h"
 #include "lzo1x_emit.h"
+#include "lzo1x_wave.h"
 
 namespace {
 
@@ -70,9 +71,6 @@ constexpr uint32_t kFarPos = 0xC0000000u;        // a read position past every b
 #ifndef POM_ENC_AHEAD
 #define POM_ENC_AHEAD 2048                      // bytes the emit wave pulls into L2 ahead of the parse
 #endif
-#ifndef POM_ENC_AHEAD1
-#define POM_ENC_AHEAD1 0                        // the one-wave kernel's own read-ahead (0: none)
-#endif
 
 // The dictionary lives in LDS (4 blocks per CU: it is 32 KiB) or, with
 // scratch from the caller, in global memory: 32 KiB per resident workgroup,
@@ -87,13 +85,8 @@ constexpr uint32_t kDictBytes = (kSlots + 2) * 2 + 60;   // per workgroup, 64-by
 // load out of range: no memory request), and the 32 KiB region needs no
 // zeroing per block.  On C3's ITB blocks 27% of primary and 38% of secondary
 // probes read unwritten slots, and a window's dictionary lines drop from 39
-// to 15 (scripts/dbg/enc_empty_sim.c).
-#ifndef POM_ENC_OCC
-#define POM_ENC_OCC 1
-#endif
-#ifndef POM_ENC_OCC2
-#define POM_ENC_OCC2 1                          // (with POM_ENC_OCC) the secondary slot only behind a written primary
-#endif
+// to 15 (scripts/dbg/enc_empty_sim.c).  The secondary slot is read only behind
+// a written primary one.
 static_assert(kDictBytes % 64 == 0, "dictionary regions stay 64-byte aligned");
 // Scratch: [0, kScratchHead) the block ticket counter (u32, zeroed by the
 // launcher when the grid is smaller than the batch), then one dictionary
@@ -108,7 +101,7 @@ struct __attribute__((aligned(16))) EncLdsT {
     // now -- 50-odd lanes writing one LDS address serialised -- and the
     // entries stay only to keep the measured layout)
     uint16_t dict[GD ? 2 : kSlots + 2]; // last probe position per hash slot: position - base + 1 (0 = empty)
-    uint32_t occ[GD && POM_ENC_OCC ? kSlots / 32 : 1];  // global dictionary: the slots this block wrote
+    uint32_t occ[GD ? kSlots / 32 : 1];  // global dictionary: the slots this block wrote
     uint32_t claim[kClaim + 1];     // (window tag << 8 | lowest posting lane) per hashed slot
     uint4 tok[kTok + 1];            // {literal start, literal count, match length (0: tail), offset}
     uint8_t stage[kStage];          // emitter output ring
@@ -123,61 +116,41 @@ static_assert(sizeof(EncLdsT<false>) * 4 <= 160 * 1024, "LDS budget");
 static_assert(sizeof(EncLdsT<true>) * POM_ENC_RESIDENT <= 160 * 1024, "LDS budget");
 
 // Dictionary access: S.dict (LDS) or the workgroup's region in global memory.
-// Probes are agent-scope relaxed atomic loads (global_load_ushort sc1): served
-// by L2, never by a stale vector-L1 line, so a probe sees this wave's earlier
-// dictionary stores.  Non-temporal probes (round 2 until the last build) are as
-// exact but mark the lines evict-first in L2: the 512 dictionaries of an XCD then
-// miss L2 far more often, and the C3 compress kernel took 2.23 instead of 1.84 ms.
-#ifndef POM_CAND_AUX
-#define POM_CAND_AUX 0                          // cache policy of the candidate loads (buffer aux bits)
-#endif
-#ifndef POM_PW_AUX
-#define POM_PW_AUX 0                            // cache policy of the probe-word loads
-#endif
-#ifndef POM_ENC_PRIO
-#define POM_ENC_PRIO 1                          // one-wave kernel: wave priority by input bytes left
-#endif
+// Global probes are buffer loads with sc1 (served by L2, never by a stale
+// vector-L1 line, so a probe sees this wave's earlier dictionary stores),
+// guarded by the bitmap of written slots.  Non-temporal probes (round 2) are
+// as exact but mark the lines evict-first in L2: the 512 dictionaries of an
+// XCD then miss L2 far more often, and the C3 compress kernel took 2.23
+// instead of 1.84 ms.
 #ifndef POM_ENC_PRIO_STEP
-#define POM_ENC_PRIO_STEP 8192
-#endif
-#ifndef POM_DICT_LOAD
-#define POM_DICT_LOAD 2                         // probe loads: 0 non-temporal, 1 plain, 2 agent-scope atomic
+#define POM_ENC_PRIO_STEP 8192                  // one-wave kernel: wave priority steps down every this many input bytes left
 #endif
 typedef __attribute__((address_space(1))) uint16_t gu16;
 template <bool GD>
 struct Dict {
     uint16_t* lds;
     gu16* g;
-    uint32_t* occ;                  // (POM_ENC_OCC) EncLdsT::occ
-    __amdgpu_buffer_rsrc_t rs;      // (POM_ENC_OCC) the region g, kSlots u16
+    uint32_t* occ;                  // (GD) EncLdsT::occ
+    __amdgpu_buffer_rsrc_t rs;      // (GD) the region g, kSlots u16
     __device__ __forceinline__ bool written(uint32_t slot) const
     {
         return (occ[slot >> 5] >> (slot & 31u)) & 1u;
     }
-    // (POM_ENC_OCC) the slot's entry if rd, else 0 with no memory request (a
-    // buffer load out of range); sc1: L1 bypassed, as the atomic loads below
+    // (GD) the slot's entry if rd, else 0 with no memory request (a buffer
+    // load out of range); sc1: L1 bypassed
     __device__ __forceinline__ uint32_t get_if(uint32_t slot, bool rd) const
     {
         return __builtin_amdgcn_raw_buffer_load_b16(rs, rd ? 2u * slot : 0x80000000u, 0, 16);
     }
     __device__ __forceinline__ uint32_t get(uint32_t slot) const
     {
-        if (GD && POM_ENC_OCC)
+        if (GD)
             return get_if(slot, written(slot));
-        if (GD) {
-#if POM_DICT_LOAD == 1
-            return g[slot];
-#elif POM_DICT_LOAD == 2
-            return __hip_atomic_load((uint16_t*)(g + slot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-            return __builtin_nontemporal_load(g + slot);
-#endif
-        }
         return lds[slot];
     }
     __device__ __forceinline__ void put(uint32_t slot, uint32_t v) const
     {
-        if (GD && POM_ENC_OCC)
+        if (GD)
             __hip_atomic_fetch_or(occ + (slot >> 5), 1u << (slot & 31u), __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_WORKGROUP);
         if (GD)
@@ -185,7 +158,7 @@ struct Dict {
         else
             lds[slot] = (uint16_t)v;
     }
-    // dwords 2i, 2i+1 of the table as one u32 (zeroing, re-basing)
+    // entries 2i, 2i+1 of the table as one u32 (re-basing)
     __device__ __forceinline__ uint32_t get2(uint32_t i) const
     {
         if (GD)
@@ -201,43 +174,9 @@ struct Dict {
     }
 };
 
-__device__ __forceinline__ uint32_t lane_id() { return emit::lane(); }
 __device__ __forceinline__ uint32_t claim_index(uint32_t slot) { return (slot ^ (slot >> 9)) & (kClaim - 1); }
 
-// Inclusive prefix sum over the wave: DPP row shifts inside each 16-lane row,
-// then the row totals via readlane (no LDS round trip; lzo1x_decode_fast.hip
-// scans the same way).
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
-    const uint32_t r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31),
-                   r2 = __builtin_amdgcn_readlane(v, 47);
-    const uint32_t row = lane_id() >> 4;
-    v += (row >= 1 ? r0 : 0u) + (row >= 2 ? r1 : 0u) + (row >= 3 ? r2 : 0u);
-    return v;
-}
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __ballot(p); }
-// Lane masks straight from a v_cmp (a ballot of a compound bool costs a
-// v_cndmask and a v_cmp more): active lanes with a == b, a < b, a >= b.
-__device__ __forceinline__ uint64_t mask_eq(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 32); }
-__device__ __forceinline__ uint64_t mask_lt(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 36); }
-__device__ __forceinline__ uint64_t mask_ge(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 35); }
 __device__ __forceinline__ void wave_order() { emit::order(); }
-
-__device__ __forceinline__ uint32_t lds_load(const uint32_t* p)
-{
-    return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_store(uint32_t* p, uint32_t v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-typedef __attribute__((address_space(1))) const uint32_t gdword;
 
 // The block as a raw buffer: the aligned dwords from the one holding byte 0
 // through the one holding byte n-1.  Reads past it return 0 in hardware (the
@@ -262,7 +201,7 @@ __device__ __forceinline__ BlockSrc block_src(const uint8_t* in, uint32_t n)
 // NW little-endian dwords of the block starting at byte pos (any alignment).
 // Aligned dwords lying wholly past the block's last byte read as 0: callers
 // cap every comparison at the block end.
-template <int NW, int AUX = 0>
+template <int NW>
 __device__ __forceinline__ void load_at(const BlockSrc& B, uint32_t pos, uint32_t (&w)[NW])
 {
     const uint32_t a = pos + B.sh0;
@@ -270,7 +209,7 @@ __device__ __forceinline__ void load_at(const BlockSrc& B, uint32_t pos, uint32_
     uint32_t r[NW + 1];
 #pragma unroll
     for (int i = 0; i <= NW; i++)
-        r[i] = __builtin_amdgcn_raw_buffer_load_b32(B.rs, a0 + 4 * i, 0, AUX);
+        r[i] = __builtin_amdgcn_raw_buffer_load_b32(B.rs, a0 + 4 * i, 0, 0);
 #pragma unroll
     for (int i = 0; i < NW; i++)
         w[i] = __builtin_amdgcn_alignbyte(r[i + 1], r[i], a & 3u);
@@ -281,9 +220,6 @@ __device__ __forceinline__ void load_at(const BlockSrc& B, uint32_t pos, uint32_
 #endif
 #ifndef POM_ENC_PATHMAX
 #define POM_ENC_PATHMAX 6                        // matches the path walk takes per window
-#endif
-#ifndef POM_ENC_BATCH
-#define POM_ENC_BATCH 1                          // the emit wave writes up to 64 tokens per pass
 #endif
 #ifndef POM_ENC_FWD
 #define POM_ENC_FWD 8                            // claim conflicts resolved in place per window
@@ -396,8 +332,8 @@ struct Emitter {
         const uint32_t msz = m2 ? 2u : shortlen ? 3u : 4u;
         const uint32_t sz = hdr + r + msz;
         const uint32_t adv = r + L;
-        const uint32_t iadv = wave_incl_sum(adv);
-        const uint32_t isz = wave_incl_sum(sz);
+        const uint32_t iadv = wave_incl_scan(adv);
+        const uint32_t isz = wave_incl_scan(sz);
         const uint32_t pk = pos + iadv - adv;              // input position of token k
         const uint32_t budget = e.smask + 1 - (e.op - e.flushed) - 4 - kLitMax;   // (- kLitMax: see the literals)
         // (every test evaluated: no short-circuit exec-mask cascade)
@@ -485,8 +421,7 @@ struct Emitter {
     __device__ bool drain(uint32_t prod, uint32_t* out_len, int32_t* status, uint32_t b)
     {
         while (ct < prod) {
-#ifndef POM_ENC_NOEMIT
-            if (POM_ENC_BATCH && !poisoned) {
+            if (!poisoned) {                         // up to 64 tokens per pass
                 const uint32_t nb = batch(prod);
                 if (nb) {
                     ct += nb;
@@ -494,7 +429,6 @@ struct Emitter {
                     continue;
                 }
             }
-#endif
             const uint4 t = S.tok[ct % kTok];
             ct++;
             // Every token must continue where the last one ended and stay in
@@ -514,13 +448,6 @@ struct Emitter {
                 }
                 return true;
             }
-#ifdef POM_ENC_NOEMIT
-            if (POM_ENC_NOEMIT) {                    // (timing experiment only: no output)
-                pos += t.y + t.z;
-                lds_store(&S.cons, ct);
-                continue;
-            }
-#endif
             if (!poisoned) {
                 if (t.y) {
                     emit::lit_header(e, t.y);
@@ -573,24 +500,10 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
     } while (0)
     uint32_t tp = 0;                                // tokens produced
     uint32_t cons_seen = 0;
-    // (FUSED, POM_ENC_AHEAD1) lines up to that many bytes past the window go
-    // to L2, one dword per 128-B line.  Off by default: a wave's loads retire
-    // in order, so the window after such a load waits for its miss, and the
-    // distance (0 / 2 / 4 KiB) moved C3 by under 1%.
-    const uintptr_t pf_lines = (uintptr_t)in & ~(uintptr_t)127;
-    const uintptr_t pf_last = ((uintptr_t)in + n - 1) & ~(uintptr_t)3;
-    uint32_t pf = 0, pf_acc = 0, pf_new = 0;
-    auto prefetch = [&](uint32_t at) {
-        pf_acc ^= pf_new;
-        pf_new = 0;
-        const uint32_t ahead = at + POM_ENC_AHEAD1;
-        const uint32_t want = ahead < n + 127 ? ahead : n + 127;
-        for (; pf < want; pf += 128 * kWave) {
-            const uintptr_t a = pf_lines + pf + 128 * l;
-            if (a <= pf_last)
-                pf_new ^= *(gdword*)a;
-        }
-    };
+    // (FUSED: the one-wave kernel has no read-ahead of its own.  A wave's
+    // loads retire in order, so the window after such a load waits for its
+    // miss, and the distance (0 / 2 / 4 KiB) moved C3 by under 1%, DESIGN.md
+    // §3.3.)
     auto push = [&](uint32_t from, uint32_t nlit, uint32_t mlen, uint32_t off) {
         if (STAMPS)
             acc[EC_TOKENS] += 1;
@@ -614,7 +527,7 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
     const BlockSrc B = block_src(in, n);
     uint32_t ii = 0;                                // first byte not yet emitted
     if (n > 13) {                                   // lib/minilzo.c:3167-3173
-        if (GD && POM_ENC_OCC) {
+        if (GD) {
             for (uint32_t s = l; s < kSlots / 32; s += kWave)
                 S.occ[s] = 0;                       // zero-filled wrkmem: all EMPTY
         } else {
@@ -623,8 +536,6 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
         }
         for (uint32_t s = l; s < kClaim; s += kWave)
             S.claim[s] = 0xFFFFFFFFu;               // (tag 0xFFFFFF: no window has it)
-        if (GD && !POM_ENC_OCC)
-            __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): the table is zero in L2
         wave_order();
         const uint32_t ip_end = n - 13;             // lib/minilzo.c:2929
         uint32_t ip = 4;
@@ -641,7 +552,6 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
         for (;;) {
             if (STAMPS)
                 acc[EC_WINDOWS] += 1;
-#if POM_ENC_PRIO
             // (one-wave kernel, one block per workgroup) blocks that are behind
             // (more input left) get the issue slots first, so the workgroups of
             // a CU finish together.  The priority steps down at most three
@@ -658,7 +568,6 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                 }
                 prio_ip = q ? n - q * st + 1 : 0xFFFFFFFFu;     // left < q * st from there on
             }
-#endif
             if (ip + kWave - base >= 0xFFFFu) {     // this window's positions would not fit
                 const uint32_t nb = (ip - (kM4MaxOffset + 1)) / kRebase * kRebase;
                 const uint32_t delta = nb - base;
@@ -674,10 +583,8 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                 wave_order();
                 base = nb;
             }
-            if (FUSED && POM_ENC_AHEAD1)
-                prefetch(ip);
-            else if (!FUSED && POM_ENC_AHEAD)
-                S.ip = ip;
+            if (!FUSED && POM_ENC_AHEAD)
+                S.ip = ip;                          // (the emit wave reads ahead from here)
             const uint32_t p = ip + l;
             const bool active = l == 0 || p < ip_end;   // the first probe always runs
             // (every lane probes; an inactive one ends with no candidate)
@@ -685,12 +592,12 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                                                    (pw[0] >> 16) & 0xFF, pw[0] >> 24);
             const uint32_t h2 = emit::slot_secondary(h1);
             uint32_t e1, e2;
-            if (GD && POM_ENC_OCC) {
+            if (GD) {
                 // (no load for a slot never written, for an inactive lane, or
                 // for the secondary slot of an empty primary: v1 is false then)
                 const bool r1 = active && D.written(h1);
                 e1 = D.get_if(h1, r1);
-                e2 = D.get_if(h2, POM_ENC_OCC2 ? r1 && D.written(h2) : D.written(h2));
+                e2 = D.get_if(h2, r1 && D.written(h2));
             } else {
                 e1 = D.get(h1);
                 e2 = D.get(h2);
@@ -712,8 +619,8 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
             // checked, no memory request; the secondary candidate is only
             // ever compared when the primary one is more than M2_MAX_OFFSET
             // back, lib/minilzo.c:2946-2949)
-            load_at<kCmpW, POM_CAND_AUX>(B, v1 ? w1 : kFarPos, c1w);
-            load_at<kCmpW, POM_CAND_AUX>(B, v2 && p - w1 > kM2MaxOffset ? w2 : kFarPos, c2w);
+            load_at<kCmpW>(B, v1 ? w1 : kFarPos, c1w);
+            load_at<kCmpW>(B, v2 && p - w1 > kM2MaxOffset ? w2 : kFarPos, c2w);
             const uint32_t b3 = pw[0] >> 24;
             // (selects, no branches)
             const bool c1pass = v1 && (p - w1 <= kM2MaxOffset || (c1w[0] >> 24) == b3);
@@ -806,7 +713,7 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
             uint32_t npw[kCmpW];
             const uint32_t end0 = end;
             if (FUSED)
-                load_at<kCmpW, POM_PW_AUX>(B, ip + end0 + l, npw);
+                load_at<kCmpW>(B, ip + end0 + l, npw);
             ESTAMP(EP_PATH);
             // ---- exactness: fixed per-lane flags, and forwarding ---------------
             // Path lane l read h1 (and h2 when use2) and writes slot; it is
@@ -898,7 +805,7 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
             }
             const uint64_t keep = end >= 64 ? ~0ull : ((1ull << end) - 1);
             if (!FUSED || end != end0)
-                load_at<kCmpW, POM_PW_AUX>(B, ip + end + l, npw);
+                load_at<kCmpW>(B, ip + end + l, npw);
 
             ESTAMP(EP_FWDR);
             // ---- tokens for the matches before the cut ------------------------
@@ -946,13 +853,8 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
             }
             // UPDATE_I of every path lane before the cut but the superseded ones: their slots are distinct
             ESTAMP(EP_TOK);
-            if (GD) {
-                if ((path & keep & ~superseded) >> l & 1ull)
-                    D.put(slot, p - base + 1);
-            } else {
-                if ((path & keep & ~superseded) >> l & 1ull)
-                    D.put(slot, p - base + 1);
-            }
+            if ((path & keep & ~superseded) >> l & 1ull)
+                D.put(slot, p - base + 1);
             wave_order();
             ESTAMP(EP_DICT);
             if (done)
@@ -966,11 +868,8 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
         }
     }
     push(ii, n - ii, 0, 0);                          // tail + EOF
-    if (FUSED) {
+    if (FUSED)
         E->drain(tp);                                // through the tail: out_len, status set
-        if (pf_acc == 0x9E3779B9u)                   // (keeps the prefetch loads; never matters)
-            S.sink = pf_acc;
-    }
 #undef ESTAMP
 }
 

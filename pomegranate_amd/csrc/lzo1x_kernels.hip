@@ -18,6 +18,7 @@
 
 #include "lzo_mi355x_kernels.h"
 #include "lzo1x_emit.h"
+#include "lzo1x_wave.h"
 
 namespace {
 
@@ -30,9 +31,6 @@ constexpr int E_LOOKBEHIND_OVERRUN = -6;
 constexpr int E_EOF_NOT_FOUND = -7;
 constexpr int E_INPUT_NOT_CONSUMED = -8;
 
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __ballot(p); }
 __device__ __forceinline__ uint32_t ctz64(uint64_t m) { return (uint32_t)__builtin_ctzll(m); }
 // Compiler-only ordering point between LDS passes of one wave: the LDS unit
 // executes one wave's DS instructions in issue order, so read-after-write

@@ -79,7 +79,8 @@ for stamp in ((False,) if a.nostamps else (False, True)):
 if a.nostamps:
     sys.exit(0)
 st = stamps.view(nb, SLOTS).double().cpu().numpy()
-# order of the kernel's PH_* / CN_* enum (lzo1x_decode_fast.hip)
+# order of the kernel's PH_* / CN_* enum (lzo1x_decode_fast.hip); p_duty is
+# retired (the parser no longer stores output) and reads 0, its index stays
 phases = ["stage", "pass1", "pwalk", "merge", "count", "write", "p_slotwait", "p_duty",
           "e_wait", "wload", "wscan", "src_issue", "fwd", "src_commit+wop", "batch",
           "space", "flags", "gather", "publish"]
@@ -105,6 +106,8 @@ for b in np.nonzero(rs)[0][:4]:
     ops_q = slot[(q % kslots) * (len(slot) // kslots): (q % kslots + 1) * (len(slot) // kslots)]
     np.save(os.path.join(ROOT, "gpurun_out", f"refused_b{b}_q{q}.npy"), ops_q)
     print("refused block", int(b), "reason", int(rs[b]), "piece", q, "window", w0)
+# the kernel's RS_* enum by index; space, landed and writer are retired (they
+# cannot occur any more) and keep their numbers for recorded profiles
 names = ["none", "off_end", "bad", "ops", "dead", "ewait", "overrun", "lookbehind", "space", "landed", "head",
-         "writer"]
+         "writer", "pool"]
 print("refusals:", {names[r]: int((rs == r).sum()) for r in np.unique(rs) if r})

@@ -122,7 +122,7 @@ def test_manifest_batches_bench_encoder(dev, gu, manifest, name):
 
 def test_bench_encoder_dirty_scratch_reused_dictionaries(dev, gu, oracle):
     """The bench encoder's dictionaries need no zeroing (round 6: a per-block
-    LDS bitmap of written slots, POM_ENC_OCC).  Twice as many blocks as
+    LDS bitmap of written slots, EncLdsT::occ).  Twice as many blocks as
     resident workgroups, so each workgroup codes a second block in the region
     its first one filled, and every block is a copy of one of two contents:
     a stale entry of the earlier block would point at equal bytes and turn
