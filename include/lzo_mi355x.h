@@ -46,7 +46,10 @@ void lzo_mi355x_debug_reload(void);
  * than the grid, reset by the call on `stream`), then, for batches of more
  * blocks than resident workgroups, 4 bytes a block for the start order
  * (largest blocks first, sorted by the call on `stream`); or NULL
- * (dictionaries in LDS: 4 blocks per CU).  No initial contents are required. */
+ * (dictionaries in LDS: 4 blocks per CU).  No initial contents are required.
+ * A block whose stream does not fit dst_cap[b] gets LZO_E_OUTPUT_OVERRUN, and
+ * out_len[b] is then the length it would have needed; nothing is written past
+ * dst_cap[b]. */
 int lzo_mi355x_compress_dev(const uint8_t *src, const uint64_t *src_off,
                             const uint32_t *src_len, uint8_t *dst,
                             const uint64_t *dst_off, const uint32_t *dst_cap,

@@ -639,6 +639,11 @@ __device__ __forceinline__ uint4 global_read16(const uint8_t* p, uint32_t lo, ui
     uint32_t w[5];
     // all five loads are written unconditionally: a dword outside [i0, i1]
     // reads dword i0 or i1 again and is then dropped
+    // (hi >= 1, so hi + sh - 1 cannot wrap: both callers sit under `live`, where
+    // the chunk holds len >= 1 bytes of its op -- an op of L bytes owns
+    // ceil(L / 16) chunks, none when L is 0.  The first passes lo = 0 and hi = p
+    // in 1..15, n1 = p - r0 >= 1 (r0 < p) or len; the second passes lo = n1 and
+    // hi = len only under `two`, which is n1 < len)
     const uint32_t i0 = (lo + sh) >> 2, i1 = (hi + sh - 1) >> 2;
 #pragma unroll
     for (uint32_t i = 0; i < 5; i++) {
