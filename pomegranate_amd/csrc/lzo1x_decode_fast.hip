@@ -51,6 +51,7 @@
 #include <stdint.h>
 
 #include "lzo_mi355x_kernels.h"
+#include "lzo1x_grammar.h"
 #include "lzo1x_wave.h"
 
 namespace {
@@ -111,10 +112,8 @@ constexpr uint32_t kMirror = 32;                 // ring[0, 16) mirrored after i
 constexpr uint32_t kSrcBytes = POM_SRCBUF;       // per-window copy of literal spans and far sources
 constexpr uint32_t kSrcDw = kSrcBytes / 4;
 static_assert(kSrcDw <= 4 * kWave, "source copy: at most 4 dwords per lane");
-constexpr uint32_t kLitFlag = 0x80000000u;
 constexpr uint32_t kLinHbm = 0x4000;             // linear source addresses from here: input in HBM
 constexpr uint32_t kMaxOpLen = 1u << 25;         // 64 ops per window cannot wrap 32 bits
-constexpr int32_t kFallback = 0x7FFF0001;        // status: exact decoder pending
 constexpr uint32_t kInfoEof = 1u << 16;          // piece info: the piece ends with EOF
 constexpr uint32_t kInfoErr = 1u << 17;          // piece info: the block needs the exact decoder
 // A step covers at most 64 chunks of 16 bytes: an op read by a step whose
@@ -127,11 +126,7 @@ constexpr uint32_t kStepSpan = 16 * kWave + 16;
 enum { RS_NONE, RS_OFF_END, RS_BAD, RS_OPS, RS_DEAD, RS_EWAIT, RS_OVERRUN, RS_LOOKBEHIND,
        RS_SPACE, RS_LANDED, RS_HEAD, RS_WRITER, RS_POOL };
 
-// parse states (instruction starts)
-constexpr uint32_t ST_A = 0;   // top: t < 16 is a literal run
-constexpr uint32_t ST_B = 1;   // after a literal run: t < 16 is a 3-byte M1 (dist > 0x800)
-constexpr uint32_t ST_C = 2;   // after trailing literals: t < 16 is a 2-byte M1
-constexpr uint32_t ST_F = 3;   // first byte of the stream (lib/minilzo.c:3357)
+// (parse states ST_A/B/C/F, the instruction Lzo1xIns: lzo1x_grammar.h)
 constexpr uint32_t kPosEnd = 0xFFFFFFF0u;        // exit marker: EOF reached / dead path
 // walk outcome
 constexpr uint32_t FL_OK = 0;                    // reached the segment end
@@ -143,7 +138,7 @@ struct __attribute__((aligned(16))) FastLds {
     // executor
     uint32_t ring[(kRing + kMirror) / 4];
     uint32_t src[kSrcDw];     // this window's literal spans and far match sources
-    uint4 wop[kWave];         // window op: {o, source base (| kLitFlag: linear), first 16-B chunk, L}
+    uint4 wop[kWave];         // window op: {o, source base (| kLzoLit: linear), first 16-B chunk, L}
     uint2 wper[kWave];        // window op: {period, floor((2^32-1)/period)}
     uint32_t flags[kWave + 4];  // per-step chunk tags (src_issue: per-dword byte flags); [kWave]: spare
                               // (+4: the fields after it stay 16-byte aligned)
@@ -248,180 +243,46 @@ __device__ __forceinline__ uint32_t rdin(const FastLds& s, const Blk& k, uint32_
     return *((__attribute__((address_space(1))) const uint8_t*)(k.in + pos));
 }
 
-// One instruction from (pos, st).  Produces up to two ops (A: literal run or
-// match; B: trailing literals) and the next point.  `bad` reports reads past
-// the end of the input, literal runs past the end, or an EOF marker that is
-// not the final instruction; `eof` the EOF marker (lib/minilzo.c:3580).
-struct Step {
-    uint32_t pos, st;
-    uint32_t aL, aS;        // op A: length, source (literal: kLitFlag | in pos; match: dist)
-    uint32_t bL, bS;        // op B (bL == 0: none)
-    bool eof, bad;
-};
-
-__device__ __forceinline__ uint32_t read_ext(const FastLds& s, const Blk& k, uint32_t& pos,
-                                             uint32_t base, bool& bad)
-{
-    uint32_t v = 0;
-    while (pos < k.z && rdin(s, k, pos) == 0) {
-        v += 255;
-        pos++;
-    }
-    if (pos >= k.z) {
-        bad = true;
-        return 0;
-    }
-    v += base + rdin(s, k, pos);
-    pos++;
-    return v;
-}
-
+// One instruction from (pos, st), general form (lzo1x_decode_general of
+// lzo1x_grammar.h: long extensions with no cap on the zero run, bytes past
+// the staging window through rdin).
 // (k by value: a noinline callee reached from divergent code must not read
 // its arguments from the caller's scratch)
-__device__ __noinline__ Step decode_one(const FastLds& s, const Blk k, uint32_t pos, uint32_t st)
+__device__ __noinline__ Lzo1xIns decode_one(const FastLds& s, const Blk k, uint32_t pos, uint32_t st)
 {
-    Step r;
-    r.aL = r.bL = 0;
-    r.aS = r.bS = 0;
-    r.eof = r.bad = false;
-    uint32_t t = rdin(s, k, pos);
-    if (pos >= k.z)
-        r.bad = true;
-    if (st == ST_F) {
-        if (t > 17) {
-            const uint32_t n = t - 17;
-            r.aL = n;
-            r.aS = kLitFlag | (pos + 1);
-            r.pos = pos + 1 + n;
-            r.st = n < 4 ? ST_C : ST_B;
-            if (r.pos > k.z)
-                r.bad = true;
-            return r;
-        }
-        st = ST_A;
-    }
-    uint32_t L, d;
-    if (t < 16 && st == ST_A) {                       // literal run, :3367-3414
-        pos++;
-        if (t == 0)
-            t = read_ext(s, k, pos, 15, r.bad);
-        const uint32_t n = t + 3;
-        r.aL = n;
-        r.aS = kLitFlag | pos;
-        r.pos = pos + n;
-        r.st = ST_B;
-        if (r.pos > k.z || r.pos < pos)
-            r.bad = true;
-        return r;
-    }
-    if (t < 16) {                                     // M1 forms, :3416-3443 / :3600-3612
-        d = (st == ST_B ? 0x801u : 1u) + (t >> 2) + (rdin(s, k, pos + 1) << 2);
-        L = st == ST_B ? 3u : 2u;
-        pos += 2;
-    } else if (t >= 64) {                             // M2
-        d = 1 + ((t >> 2) & 7) + (rdin(s, k, pos + 1) << 3);
-        L = (t >> 5) + 1;
-        pos += 2;
-    } else if (t >= 32) {                             // M3
-        L = t & 31;
-        pos++;
-        if (L == 0)
-            L = read_ext(s, k, pos, 31, r.bad);
-        L += 2;
-        d = 1 + ((rdin(s, k, pos) | (rdin(s, k, pos + 1) << 8)) >> 2);
-        pos += 2;
-    } else {                                          // M4 / EOF
-        uint32_t dd = (t & 8) << 11;
-        L = t & 7;
-        pos++;
-        if (L == 0)
-            L = read_ext(s, k, pos, 7, r.bad);
-        L += 2;
-        dd += (rdin(s, k, pos) | (rdin(s, k, pos + 1) << 8)) >> 2;
-        pos += 2;
-        if (dd == 0) {
-            r.eof = true;
-            r.pos = pos;
-            r.st = ST_A;
-            if (pos != k.z)
-                r.bad = true;                         // INPUT_NOT_CONSUMED / OVERRUN
-            return r;
-        }
-        d = dd + 0x4000;
-    }
-    if (pos > k.z)
-        r.bad = true;
-    r.aL = L;
-    r.aS = d;
-    const uint32_t tl = rdin(s, k, pos - 2) & 3;      // match_done, :3650-3653
-    if (tl) {
-        r.bL = tl;
-        r.bS = kLitFlag | pos;
-        pos += tl;
-        r.st = ST_C;
-        if (pos > k.z)
-            r.bad = true;
-    } else
-        r.st = ST_A;
-    r.pos = pos;
-    return r;
+    return lzo1x_decode_general([&](uint32_t p) { return rdin(s, k, p); }, Lzo1xZeroRun{kLzoZerosAny},
+                                pos, st, k.z);
 }
 
-// Branch-free form of decode_one for the common case: the instruction lies in
-// the staged input and any length extension is a single non-zero byte.  One
-// LDS round trip (two aligned dwords -> 4 bytes at pos), then selects; lanes
-// decoding different instruction kinds do not diverge.  Falls back to
-// decode_one otherwise (long extensions, input beyond the staging window).
-// SPEC: speculative use -- never take the slow path; report it as `slow`
-// (the caller restarts or re-walks exactly) instead.
-template <bool SPEC = false>
-__device__ __forceinline__ Step decode_step(const FastLds& s, const Blk& k, uint32_t pos, uint32_t st,
-                                            bool* slow = nullptr)
+// The staged instruction word for the branch-free form (lzo1x_decode_word):
+// the instruction lies in the staged input when inwin.  One LDS round trip
+// (two aligned dwords -> 4 bytes at pos; bytes past z read 0 from the stage),
+// read from a clamped offset and ignored when !inwin.
+__device__ __forceinline__ bool stage_dwords(const FastLds& s, const Blk& k, uint32_t pos, uint32_t& w0,
+                                             uint32_t& w1)
 {
     const uint32_t rel = pos - k.P;
     const bool inwin = rel + 8 <= kStageBytes && pos < k.z;
-    // Every field of a non-extended instruction lies in its first 4 bytes
-    // (t, then at most 3 more; bytes past z read 0 from the stage): two LDS
-    // dwords, one alignbyte, then bit-field extracts -- no 64-bit shifts.
-    // (The dwords are read from a clamped offset; ignored when !inwin.)
     const uint32_t wi = inwin ? rel >> 2 : 0u;
-    const uint32_t lo = __builtin_amdgcn_alignbyte(s.stage[wi + 1], s.stage[wi], rel & 3u);
-    const uint32_t t = lo & 0xFFu, b1 = __builtin_amdgcn_ubfe(lo, 8, 8);
-    const bool flit = st == ST_F && t > 17;                        // :3357-3365
-    const uint32_t se = st == ST_F ? ST_A : st;
-    const bool lit = !flit && se == ST_A && t < 16;                // :3367-3414
-    const bool m1 = !flit && !lit && t < 16;
-    const bool m2 = !flit && t >= 64;
-    const bool m3 = !flit && t >= 32 && t < 64;
-    const bool m4 = !flit && t >= 16 && t < 32;
-    const bool ext = (lit && t == 0) || (m3 && (t & 31) == 0) || (m4 && (t & 7) == 0);
-    const bool needs_slow = !inwin || (ext && b1 == 0);            // 255-chunk extension
-    const uint32_t e = ext ? 1u : 0u;
-    const uint32_t o16 = __builtin_amdgcn_ubfe(lo, 8u + 8u * e, 16);   // bytes 1+e, 2+e
-    const uint32_t dd4 = ((t & 8u) << 11) + (o16 >> 2);
-    const uint32_t used = (m1 || m2) ? 2u : 3u + e;                // match instruction bytes
-    const uint32_t tl = __builtin_amdgcn_ubfe(lo, 8u * (used - 2u), 2);   // match_done, :3650
-    const uint32_t nlit = flit ? t - 17 : (ext ? 15u + b1 : t) + 3u;
-    const uint32_t L = m1 ? (se == ST_B ? 3u : 2u)
-                     : m2 ? (t >> 5) + 1u
-                     : m3 ? (ext ? 31u + b1 : (t & 31u)) + 2u
-                          : (ext ? 7u + b1 : (t & 7u)) + 2u;
-    const uint32_t d = m1 ? (se == ST_B ? 0x801u : 1u) + (t >> 2) + (b1 << 2)
-                     : m2 ? 1u + ((t >> 2) & 7u) + (b1 << 3)
-                     : m3 ? 1u + (o16 >> 2) : dd4 + 0x4000u;
-    const bool eof = m4 && dd4 == 0;                               // :3580
-    const bool islit = flit || lit;
-    const uint32_t hdr = flit ? 1u : 1u + e;                       // literal-run header bytes
-    Step r;
-    r.eof = eof;
-    r.aL = eof ? 0u : islit ? nlit : L;
-    r.aS = islit ? kLitFlag | (pos + hdr) : d;
-    r.bL = (islit || eof) ? 0u : tl;
-    r.bS = kLitFlag | (pos + used);
-    r.pos = islit ? pos + hdr + nlit : pos + used + (eof ? 0u : tl);
-    r.st = islit ? (flit && nlit < 4 ? ST_C : ST_B) : (tl && !eof ? ST_C : ST_A);
-    r.bad = eof ? r.pos != k.z : r.pos > k.z;
-    if (__builtin_expect(needs_slow, 0)) {
+    w0 = s.stage[wi];
+    w1 = s.stage[wi + 1];
+    return inwin;
+}
+
+// Per-lane decode: the branch-free form, decode_one for what it does not
+// cover (long extensions, input beyond the staging window).
+// SPEC: speculative use -- never take the slow path; report it as `slow`
+// (the caller restarts or re-walks exactly) instead.
+template <bool SPEC = false>
+__device__ __forceinline__ Lzo1xIns decode_step(const FastLds& s, const Blk& k, uint32_t pos, uint32_t st,
+                                                bool* slow = nullptr)
+{
+    uint32_t w0, w1;
+    bool general;
+    const bool inwin = stage_dwords(s, k, pos, w0, w1);
+    const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, (pos - k.P) & 3u);
+    Lzo1xIns r = lzo1x_decode_word<true>(lo, pos, st, k.z, general);
+    if (__builtin_expect(!inwin || general, 0)) {
         if (SPEC) {
             r.pos = pos;
             r.st = st;
@@ -439,51 +300,21 @@ __device__ __forceinline__ Step decode_step(const FastLds& s, const Blk& k, uint
 // scan below walks one segment's true path with every lane at the same
 // point): the two stage dwords are made scalar with readfirstlane, so the
 // decode runs on the scalar unit -- a few SALU per field instead of a VALU
-// instruction for all 64 lanes (~55 per instruction decoded).  Same fields as
-// decode_step; the rare instructions take decode_one (per lane, all alike).
-__device__ __forceinline__ Step decode_step_u(const FastLds& s, const Blk& k, uint32_t pos, uint32_t st)
+// instruction for all 64 lanes (~55 per instruction decoded).  The walks count
+// ops only (aS, bS unused); the rare instructions take decode_one (per lane,
+// all alike).
+__device__ __forceinline__ Lzo1xIns decode_step_u(const FastLds& s, const Blk& k, uint32_t pos, uint32_t st)
 {
-    const uint32_t rel = pos - k.P;
-    const bool inwin = rel + 8 <= kStageBytes && pos < k.z;
-    const uint32_t wi = inwin ? rel >> 2 : 0u;
-    const uint32_t w0 = __builtin_amdgcn_readfirstlane(s.stage[wi]);
-    const uint32_t w1 = __builtin_amdgcn_readfirstlane(s.stage[wi + 1]);
-    const uint32_t lo = (uint32_t)((((uint64_t)w1 << 32) | w0) >> (8u * (rel & 3u)));
-    const uint32_t t = lo & 0xFFu, b1 = (lo >> 8) & 0xFFu;
-    const bool flit = st == ST_F && t > 17;                        // :3357-3365
-    const uint32_t se = st == ST_F ? ST_A : st;
-    const bool lit = !flit && se == ST_A && t < 16;                // :3367-3414
-    const bool m1 = !flit && !lit && t < 16;
-    const bool m2 = !flit && t >= 64;
-    const bool m3 = !flit && t >= 32 && t < 64;
-    const bool m4 = !flit && t >= 16 && t < 32;
-    const bool ext = (lit && t == 0) || (m3 && (t & 31) == 0) || (m4 && (t & 7) == 0);
-    const bool needs_slow = !inwin || (ext && b1 == 0);            // 255-chunk extension
-    const uint32_t e = ext ? 1u : 0u;
-    const uint32_t o16 = (lo >> (8u + 8u * e)) & 0xFFFFu;          // bytes 1+e, 2+e
-    const uint32_t dd4 = ((t & 8u) << 11) + (o16 >> 2);
-    const uint32_t used = (m1 || m2) ? 2u : 3u + e;                // match instruction bytes
-    const uint32_t tl = (lo >> (8u * (used - 2u))) & 3u;           // match_done, :3650
-    const uint32_t nlit = flit ? t - 17 : (ext ? 15u + b1 : t) + 3u;
-    const uint32_t L = m1 ? (se == ST_B ? 3u : 2u)
-                     : m2 ? (t >> 5) + 1u
-                     : m3 ? (ext ? 31u + b1 : (t & 31u)) + 2u
-                          : (ext ? 7u + b1 : (t & 7u)) + 2u;
-    const bool eof = m4 && dd4 == 0;                               // :3580
-    const bool islit = flit || lit;
-    const uint32_t hdr = flit ? 1u : 1u + e;                       // literal-run header bytes
-    Step r;
-    r.eof = eof;
-    r.aL = eof ? 0u : islit ? nlit : L;
-    r.aS = 0;                                                      // (the walks count ops only)
-    r.bL = (islit || eof) ? 0u : tl;
-    r.bS = 0;
-    r.pos = islit ? pos + hdr + nlit : pos + used + (eof ? 0u : tl);
-    r.st = islit ? (flit && nlit < 4 ? ST_C : ST_B) : (tl && !eof ? ST_C : ST_A);
-    r.bad = eof ? r.pos != k.z : r.pos > k.z;
-    if (__builtin_expect(needs_slow, 0)) {
+    uint32_t w0, w1;
+    bool general;
+    const bool inwin = stage_dwords(s, k, pos, w0, w1);
+    w0 = __builtin_amdgcn_readfirstlane(w0);
+    w1 = __builtin_amdgcn_readfirstlane(w1);
+    const uint32_t lo = (uint32_t)((((uint64_t)w1 << 32) | w0) >> (8u * ((pos - k.P) & 3u)));
+    Lzo1xIns r = lzo1x_decode_word<false>(lo, pos, st, k.z, general);
+    if (__builtin_expect(!inwin || general, 0)) {
         // (every lane decodes the same instruction: keep the fields scalar)
-        const Step q = decode_one(s, k, pos, st);
+        const Lzo1xIns q = decode_one(s, k, pos, st);
         r.pos = __builtin_amdgcn_readfirstlane(q.pos);
         r.st = __builtin_amdgcn_readfirstlane(q.st);
         r.aL = __builtin_amdgcn_readfirstlane(q.aL);
@@ -709,7 +540,7 @@ __device__ __forceinline__ WalkRes walk_true(const FastLds& S, const Blk& k, uin
             }
         }
         bool slow = false;
-        const Step r = SPEC ? decode_step<true>(S, k, pos, st, &slow) : decode_step_u(S, k, pos, st);
+        const Lzo1xIns r = SPEC ? decode_step<true>(S, k, pos, st, &slow) : decode_step_u(S, k, pos, st);
         if (SPEC && slow) {
             w.fl = FL_UNK;
             break;
@@ -850,7 +681,7 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
                     break;
                 if (act) {
                     bool slow = false;
-                    const Step r = decode_step<true>(S, k, pos, st, &slow);
+                    const Lzo1xIns r = decode_step<true>(S, k, pos, st, &slow);
                     const bool mine = pos >= c0;
                     const uint32_t bit = mine ? 1u << (pos - c0) : 0u;
                     if (r.bad || r.eof) {              // impossible guess: restart later
@@ -978,7 +809,7 @@ __device__ __forceinline__ void parser_wave(FastLds& S, Blk k, uint2* __restrict
                 uint32_t itw = 0;
                 while (p < c1 && wi < wend) {
                     itw++;
-                    const Step r = decode_step(S, k, p, s);
+                    const Lzo1xIns r = decode_step(S, k, p, s);
                     if (r.eof || r.bad) {
                         lane_err = true;               // (the scan saw ops here)
                         break;
@@ -1141,7 +972,7 @@ __device__ __forceinline__ SrcCopy src_issue(FastLds& S, const Blk& k, uint32_t 
         fc.sh |= (hbm[i] ? sh[i] : 0u) << (2 * i);
     }
     if (acc)
-        db = kLitFlag | (kSrcOff + 4u * (cum - nd) + ((litc ? ipos : db) & 3u));
+        db = kLzoLit | (kSrcOff + 4u * (cum - nd) + ((litc ? ipos : db) & 3u));
     return fc;
 }
 
@@ -1240,7 +1071,7 @@ __device__ void block_close(FastLds& S, uint32_t b, uint32_t* __restrict__ out_l
         out_len[b] = prod;
         status[b] = 0;
     } else {
-        status[b] = kFallback;
+        status[b] = LZO_MI355X_DEC_PENDING;
         out_len[b] = 0xFA110000u | lds_load(&S.why);   // (diagnostics: state 2, the executor's reason)
         const uint32_t at = atomicAdd(&fallback[0], 1u);
         fallback_ids[at] = b;
@@ -1408,7 +1239,7 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                 reason = RS_OVERRUN;
                 break;
             }
-            const bool lit = (Sv & kLitFlag) != 0;
+            const bool lit = (Sv & kLzoLit) != 0;
             const bool lb = l < nwin && !lit && Sv > o;     // LOOKBEHIND_OVERRUN
             if (wave_ballot(lb)) {
                 refuse = true;
@@ -1417,11 +1248,11 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
             }
             // ---- op descriptors: byte x of op j reads
             //   src[b + ((x - o) mod p)]   (p == 0: src[b + x - o])
-            // at linear address b (kLitFlag set: the LDS source buffer, or from
+            // at linear address b (kLzoLit set: the LDS source buffer, or from
             // kLinHbm the input in HBM) or in the output (ring / HBM).  A match
             // starts as b = o - d, p = d if it overlaps itself (d < L).
-            const uint32_t ipos = Sv & ~kLitFlag;
-            uint32_t db = lit ? kLitFlag | (kLinHbm + ipos) : o - Sv;
+            const uint32_t ipos = Sv & ~kLzoLit;
+            uint32_t db = lit ? kLzoLit | (kLinHbm + ipos) : o - Sv;
             uint32_t dp = (!lit && Sv < L) ? Sv : 0u;
             // sources older than the ring are read back from HBM: the stores
             // of those bytes (issued before their slots were reused, so
@@ -1452,7 +1283,7 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                 inv = dp ? 0xFFFFFFFFu / dp : 0u;
             for (int round = 0; round < POM_FWD_ROUNDS; round++) {
                 const uint32_t span = dp ? dp : L;
-                const bool need = l < nwin && !(db & kLitFlag) && db + span > o_first;
+                const bool need = l < nwin && !(db & kLzoLit) && db + span > o_first;
                 if (!wave_ballot(need))
                     break;
                 if (STAMPS)
@@ -1481,7 +1312,7 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
             src_commit(S, l, fc);
             // end of each output-sourced op's source span: a batch may not read
             // its own output
-            const bool outsrc = l < nwin && !(db & kLitFlag);
+            const bool outsrc = l < nwin && !(db & kLzoLit);
             const uint32_t span = dp ? dp : L;
             const uint32_t send = outsrc ? db + span : 0u;
             // Chunks: op j covers the window's 16-byte chunks cs .. cs +
@@ -1549,8 +1380,8 @@ __global__ __launch_bounds__(2 * kWave, POM_WAVES_PER_EU) void lzo1x_decode_fast
                     // ---- source bytes of the chunk ---------------------------
                     // byte i reads src[b + ((k16 + i) mod p)] (p == 0: b + k16 + i)
                     const uint32_t p = pr.x;
-                    const bool lin = (op.y & kLitFlag) != 0;
-                    const uint32_t bb = op.y & ~kLitFlag;
+                    const bool lin = (op.y & kLzoLit) != 0;
+                    const uint32_t bb = op.y & ~kLzoLit;
                     // (p == 0: the inverse is 0, so r0 stays k16 without a branch)
                     uint32_t r0 = k16 - p * (uint32_t)__umulhi(k16, pr.y);
                     r0 = min(r0, r0 - p);

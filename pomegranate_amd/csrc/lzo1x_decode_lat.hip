@@ -36,12 +36,10 @@
 #include <stdint.h>
 
 #include "lzo_mi355x_kernels.h"
+#include "lzo1x_grammar.h"
 
 namespace {
 
-constexpr uint32_t ST_A = 0, ST_B = 1, ST_C = 2, ST_F = 3;
-constexpr uint32_t kLitO = 0x80000000u;          // origin: an input position
-constexpr int32_t kFallback = 0x7FFF0001;
 constexpr uint32_t kT = 256;                     // threads per workgroup (grids)
 constexpr uint32_t kScanT = 1024;                // scan tile: kScanT threads x 4
 constexpr uint32_t kTile = 4 * kScanT;
@@ -85,6 +83,7 @@ __device__ __forceinline__ uint32_t blk_of_out(const Blks& B, uint32_t p)
     return b;
 }
 
+// (an origin with kLzoLit set is an input position, as an op's literal source)
 struct Ins {
     uint32_t L, d, lit, lsrc, next, nst, kind;   // kind: 0 ok, 1 EOF exactly at z, 2 refuse
 };
@@ -94,98 +93,22 @@ __device__ __forceinline__ uint32_t ib(const uint8_t* in, uint32_t z, uint32_t q
     return q < z ? (uint32_t)in[q] : 0u;
 }
 
-// One instruction at p in state s (lib/minilzo.c:3357-3414 literal runs,
-// 3418-3443 / 3588-3613 M1, 3447-3498 M2, 3500-3537 M3, 3538-3587 M4 / EOF,
-// 3650-3667 trailing literals).
+// One instruction at p in state s: the general form of lzo1x_grammar.h, as
+// this decoder's fields (a match with its trailing literals, or a literal
+// run alone).  Every node of a zero run would scan the rest of the run, so a
+// node gives a long length extension up (kLzoZerosLat): refused here, the
+// block goes to the exact decoder, which decodes such a stream in linear time.
+// An instruction that ends at z without being the EOF marker is refused too:
+// nothing can follow it.
 __device__ Ins decode_at(const uint8_t* in, uint32_t z, uint32_t p, uint32_t s)
 {
-    Ins x{0, 0, 0, 0, 0, ST_A, 2};
-    uint32_t q = p;
-    if (q >= z)
-        return x;
-    const uint32_t t = ib(in, z, q++);
-    // A length extension: zero bytes count 255 each.  Every node of a zero run
-    // would scan the rest of the run, so a node gives up after kExtMax zero
-    // bytes (a length past ~16 K): refused here, the block goes to the exact
-    // decoder, which decodes such a stream in linear time.
-    constexpr uint32_t kExtMax = 64;
-    auto ext = [&](uint32_t base, uint32_t& n) -> bool {
-        uint32_t v = 0;
-        for (;;) {
-            if (q >= z || v >= kExtMax * 255u)
-                return false;
-            const uint32_t b = ib(in, z, q++);
-            if (b) {
-                n = v + base + b;
-                return true;
-            }
-            v += 255;
-        }
-    };
-    if (s == ST_F) {
-        if (t > 17) {
-            x.lit = t - 17;
-            x.lsrc = q;
-            x.next = q + x.lit;
-            x.nst = x.lit >= 4 ? ST_B : ST_C;
-            x.kind = x.next < z ? 0 : 2;
-            return x;
-        }
-        s = ST_A;
-    }
-    uint32_t w;
-    if (t < 16) {
-        if (s == ST_A) {
-            uint32_t n = t;
-            if (n == 0 && !ext(15, n))
-                return x;
-            x.lit = n + 3;
-            x.lsrc = q;
-            x.next = q + x.lit;
-            x.nst = ST_B;
-            x.kind = x.next < z ? 0 : 2;
-            return x;
-        }
-        const uint32_t b1 = ib(in, z, q++);
-        x.L = s == ST_B ? 3u : 2u;
-        x.d = (s == ST_B ? 0x801u : 1u) + (t >> 2) + (b1 << 2);
-        w = t;
-    } else if (t >= 64) {
-        const uint32_t b1 = ib(in, z, q++);
-        x.L = (t >> 5) + 1;
-        x.d = 1 + ((t >> 2) & 7) + (b1 << 3);
-        w = t;
-    } else if (t >= 32) {
-        uint32_t n = t & 31;
-        if (n == 0 && !ext(31, n))
-            return x;
-        x.L = n + 2;
-        w = ib(in, z, q) | (ib(in, z, q + 1) << 8);
-        q += 2;
-        x.d = 1 + (w >> 2);
-    } else {
-        uint32_t n = t & 7;
-        if (n == 0 && !ext(7, n))
-            return x;
-        x.L = n + 2;
-        w = ib(in, z, q) | (ib(in, z, q + 1) << 8);
-        q += 2;
-        const uint32_t dd = ((t & 8) << 11) + (w >> 2);
-        if (dd == 0) {
-            x.L = 0;
-            x.next = q;
-            x.kind = q == z ? 1 : 2;
-            return x;
-        }
-        x.d = dd + 0x4000;
-    }
-    const uint32_t T = w & 3;
-    x.lit = T;
-    x.lsrc = q;
-    x.next = q + T;
-    x.nst = T ? ST_C : ST_A;
-    x.kind = x.next < z ? 0 : 2;
-    return x;
+    const Lzo1xIns r = lzo1x_decode_general([&](uint32_t q) { return ib(in, z, q); }, Lzo1xZeroRun{kLzoZerosLat},
+                                            p, s, z);
+    if (r.bad || (!r.eof && r.pos >= z))
+        return Ins{0, 0, 0, 0, 0, ST_A, 2};
+    if (r.aS & kLzoLit)
+        return Ins{0, 0, r.aL, r.aS & ~kLzoLit, r.pos, r.st, 0};
+    return Ins{r.aL, r.aS, r.bL, r.bS & ~kLzoLit, r.pos, r.st, r.eof ? 1u : 0u};
 }
 
 __device__ __forceinline__ uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
@@ -350,7 +273,7 @@ __global__ __launch_bounds__(kT) void lat_origins(const Blks B, const uint32_t* 
     for (uint32_t p = blockIdx.x * kT + threadIdx.x; p < B.C; p += gridDim.x * kT) {
         const uint32_t b = blk_of_out(B, p), pl = p - B.m[b].oo;
         if (ctl[C_BADB + b] || pl >= ctl[C_TOTB + b]) {
-            org[p] = kLitO;                      // (outside every block's output: never gathered)
+            org[p] = kLzoLit;                      // (outside every block's output: never gathered)
             continue;
         }
         uint32_t id = cover[p];
@@ -359,7 +282,7 @@ __global__ __launch_bounds__(kT) void lat_origins(const Blks B, const uint32_t* 
         const uint4 f = fld[id];
         const uint32_t o = osum[id] - tot[id] - ctl[C_BASEB + b];
         const uint32_t r = pl - o;
-        org[p] = r < f.x ? p - f.y : kLitO | (uint32_t)(B.m[b].in_off + f.w + (r - f.x));
+        org[p] = r < f.x ? p - f.y : kLzoLit | (uint32_t)(B.m[b].in_off + f.w + (r - f.x));
     }
 }
 
@@ -372,14 +295,14 @@ __global__ __launch_bounds__(kT) void lat_double(uint32_t* org, uint32_t C, uint
     bool left = false;
     for (uint32_t p = blockIdx.x * kT + threadIdx.x; p < C; p += gridDim.x * kT) {
         uint32_t o = __hip_atomic_load(org + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!(o & kLitO)) {
+        if (!(o & kLzoLit)) {
             // seven dereferences a pass: a chain shrinks 8x per launch
 #pragma unroll
             for (int i = 0; i < 7; i++)
-                if (!(o & kLitO))
+                if (!(o & kLzoLit))
                     o = __hip_atomic_load(org + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(org + p, o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            left = left || !(o & kLitO);
+            left = left || !(o & kLzoLit);
         }
     }
     if (__any(left) && (threadIdx.x & 63u) == 0)
@@ -398,7 +321,7 @@ __global__ __launch_bounds__(kT) void lat_gather(const uint8_t* __restrict__ src
         const uint32_t b = b0 + g;
         if (ctl[C_BADB + g] || stuck) {
             out_len[b] = 0xFA110000u;
-            status[b] = kFallback;
+            status[b] = LZO_MI355X_DEC_PENDING;
             fallback_ids[atomicAdd(&fallback[0], 1u)] = b;
         } else {
             out_len[b] = ctl[C_TOTB + g];
@@ -410,7 +333,7 @@ __global__ __launch_bounds__(kT) void lat_gather(const uint8_t* __restrict__ src
     for (uint32_t p = g; p < B.C; p += gridDim.x * kT) {
         const uint32_t b = blk_of_out(B, p), pl = p - B.m[b].oo;
         if (!ctl[C_BADB + b] && pl < ctl[C_TOTB + b])
-            dst[B.m[b].out_off + pl] = src[org[p] & ~kLitO];
+            dst[B.m[b].out_off + pl] = src[org[p] & ~kLzoLit];
     }
 }
 
@@ -666,7 +589,7 @@ extern "C" int lzo_mi355x_launch_decompress_lat_n(const uint8_t* src, const uint
 }
 
 // One block (the single-call path): out_len[b] / status[b] and the fallback
-// list as the other decoders (0, or 0x7FFF0001 with b appended).
+// list as the other decoders (0, or LZO_MI355X_DEC_PENDING with b appended).
 extern "C" int lzo_mi355x_launch_decompress_lat(const uint8_t* in, uint32_t z, uint8_t* out, uint32_t cap,
                                                 uint32_t* out_len, int32_t* status, uint32_t* fallback,
                                                 uint32_t* fallback_ids, uint32_t b, void* scratch,

@@ -41,6 +41,7 @@
 #include <stdint.h>
 
 #include "lzo_mi355x_kernels.h"
+#include "lzo1x_grammar.h"
 #include "lzo1x_wave.h"
 
 namespace {
@@ -56,15 +57,12 @@ constexpr uint32_t kG = 32;                      // parse segment bytes
 constexpr uint32_t kNPL = kZH / kG;              // parse lanes (wave 0)
 constexpr uint32_t kLook = 32;                   // speculative lead-in
 constexpr uint32_t kFin = 53248u;                // e >= kFin: final byte at ring[A + e - kFin]
-constexpr uint32_t kLitF = 0x80000000u;          // op source: literal ...
-constexpr uint32_t kLitG = 0x40000000u;          // ... at an input position (else a zin offset)
-constexpr int32_t kFallback = 0x7FFF0001;
+constexpr uint32_t kLitG = 0x40000000u;          // a literal source (kLzoLit) at an input position (else a zin offset)
 static_assert(kW * 8 == kNT * 64, "window: 8 bytes per thread");
 static_assert(kW + 2 * kW <= 65536u - 0xBFFFu - 1u, "pointer table [A+W, A+3W) in dead ring slots");
 static_assert(0xBFFFu + kW < kFin && kFin + kW <= 65536u, "e encoding: match pointers below final ones");
 static_assert(kNPL == kWave, "one parse wave");
 
-enum : uint32_t { ST_A = 0, ST_B = 1, ST_C = 2, ST_F = 3 };
 enum : uint32_t { TK_EOF = 1, TK_BAD = 2 };
 // piece results
 enum : uint32_t { PR_OK = 0, PR_EOF = 1, PR_FULL = 2, PR_REFUSE = 3 };
@@ -75,7 +73,7 @@ struct __attribute__((aligned(16))) WinLds {
     uint8_t ring[65536];
     uint32_t zin[kZR / 4 + 4];                   // + pad: 4-byte reads past the end
     uint32_t opp[kOpCap + 4];                    // op output start; opp[nops] = end
-    uint32_t ops[kOpCap];                        // kLitF | zin offset, or match distance
+    uint32_t ops[kOpCap];                        // kLzoLit | zin offset, or match distance
     uint32_t bmap[2][kW / 32];                   // op starts of the window
     uint32_t ctl[C_N];
     uint64_t stamp[16];                          // diagnostics (STAMPS builds)
@@ -106,195 +104,55 @@ __device__ __forceinline__ uint32_t in_byte(const WinLds& L, const Piece& k, uin
     return p < k.sEnd ? zbyte(L, k.zb + (p - k.I)) : (uint32_t)k.in[p];
 }
 
-struct Tok {
-    uint32_t pos, st;    // next instruction start
-    uint32_t aL, aS;     // op A: length, source (kLitF | input pos, or distance)
-    uint32_t bL, bS;     // op B: trailing literals (bL == 0: none)
-    uint32_t fl;         // TK_*
+// The windowed decoder's zero-run policy (lzo1x_grammar.h).  spec: a lane
+// decoding speculatively from inside a long zero run would scan the rest of
+// it, for every start in the run; its guess is refused early instead.  The
+// true path -- the frontier, counting and emitting walks -- scans each run
+// once (linear time), up to the 2^24 zeros from which the exact decoder takes
+// the block; past the staged piece, aligned 16-byte reads take the run 16
+// bytes at a time: such a read never leaves the page of the block's byte at p.
+struct WinZeroRun {
+    const Piece& k;
+    bool spec;
+    uint32_t limit;
+    __device__ __forceinline__ uint32_t bulk(uint32_t p, uint32_t z) const
+    {
+        if (!spec && p >= k.sEnd && p + 16 <= z && ((uintptr_t)(k.in + p) & 15u) == 0) {
+            const uint4 w = *(const uint4*)(k.in + p);
+            if ((w.x | w.y | w.z | w.w) == 0)
+                return 16u;
+        }
+        return 0u;
+    }
 };
 
-constexpr uint32_t kMaxExtZeros = 64;            // zero length-extension bytes a lane reads at most
-constexpr uint32_t kMaxRunZeros = 1u << 24;      // zero bytes the true path takes in one extension
-
-// One instruction at (pos, st), general form: long length extensions and
-// instructions that run past the staged piece (bytes read from HBM).  Bytes
-// at or past z read as 0 and make the instruction TK_BAD.
-__device__ __noinline__ Tok tok_slow(const WinLds& L, const Piece k, uint32_t pos, uint32_t st, bool spec)
+// One instruction at (pos, st), general form (lzo1x_decode_general): long
+// length extensions and instructions that run past the staged piece (bytes
+// read from HBM).
+// (k by value: a noinline callee reached from divergent code must not read
+// its arguments from the caller's scratch)
+__device__ __noinline__ Lzo1xIns tok_slow(const WinLds& L, const Piece k, uint32_t pos, uint32_t st, bool spec)
 {
-    Tok r;
-    r.aL = r.bL = r.aS = r.bS = 0;
-    r.fl = 0;
-    uint32_t far = 0;    // furthest byte read + 1
-    auto rd = [&](uint32_t p) -> uint32_t {
-        far = p + 1 > far ? p + 1 : far;
-        return p < k.z ? in_byte(L, k, p) : 0u;
-    };
-    // (spec: a lane decoding speculatively from inside a long zero run would
-    // scan the rest of it, for every start in the run; after kMaxExtZeros zero
-    // bytes its guess is refused instead.  The true path -- the frontier,
-    // counting and emitting walks -- scans each run once: linear time)
-    // (the true path too: a run of 2^24 zero bytes or more is refused, so the
-    // block goes to the exact decoder, which keeps the reference's 64-bit
-    // length, lib/minilzo.c:3805 -- from 16,843,009 zeros on, 255 per zero
-    // passes 2^32 and this u32 sum would wrap to a small, valid-looking length)
-    bool capped = false;
-    auto ext = [&](uint32_t& p, uint32_t base) -> uint32_t {
-        uint32_t v = 0;
-        while (p < k.z) {
-            if (v >= 255u * kMaxRunZeros) {
-                capped = true;
-                break;
-            }
-            // (past the staged piece, aligned 16-byte reads take a long zero
-            // run 16 bytes at a time: such a read never leaves the page of the
-            // block's byte at p)
-            if (!spec && p >= k.sEnd && p + 16 <= k.z && ((uintptr_t)(k.in + p) & 15u) == 0) {
-                const uint4 w = *(const uint4*)(k.in + p);
-                if ((w.x | w.y | w.z | w.w) == 0) {
-                    v += 255u * 16;
-                    p += 16;
-                    far = p > far ? p : far;
-                    continue;
-                }
-            }
-            if (rd(p) != 0)
-                break;
-            v += 255;
-            p++;
-            if (spec && v > 255u * kMaxExtZeros) {
-                capped = true;
-                break;
-            }
-        }
-        v += base + rd(p);
-        p++;
-        return v;
-    };
-    uint32_t t = rd(pos);
-    if (st == ST_F) {
-        if (t > 17) {
-            const uint32_t n = t - 17;
-            r.aL = n;
-            r.aS = kLitF | (pos + 1);
-            r.pos = pos + 1 + n;
-            r.st = n < 4 ? ST_C : ST_B;
-            goto done;
-        }
-        st = ST_A;
-    }
-    {
-        uint32_t Ln, d;
-        if (t < 16 && st == ST_A) {
-            pos++;
-            if (t == 0)
-                t = ext(pos, 15);
-            r.aL = t + 3;
-            r.aS = kLitF | pos;
-            r.pos = pos + t + 3;
-            r.st = ST_B;
-            goto done;
-        }
-        if (t < 16) {
-            d = (st == ST_B ? 0x801u : 1u) + (t >> 2) + (rd(pos + 1) << 2);
-            Ln = st == ST_B ? 3u : 2u;
-            pos += 2;
-        } else if (t >= 64) {
-            d = 1 + ((t >> 2) & 7) + (rd(pos + 1) << 3);
-            Ln = (t >> 5) + 1;
-            pos += 2;
-        } else if (t >= 32) {
-            Ln = t & 31;
-            pos++;
-            if (Ln == 0)
-                Ln = ext(pos, 31);
-            Ln += 2;
-            d = 1 + ((rd(pos) | (rd(pos + 1) << 8)) >> 2);
-            pos += 2;
-        } else {
-            uint32_t dd = (t & 8) << 11;
-            Ln = t & 7;
-            pos++;
-            if (Ln == 0)
-                Ln = ext(pos, 7);
-            Ln += 2;
-            dd += (rd(pos) | (rd(pos + 1) << 8)) >> 2;
-            pos += 2;
-            if (dd == 0) {
-                r.fl = TK_EOF;
-                r.pos = pos;
-                r.st = ST_A;
-                goto done;
-            }
-            d = dd + 0x4000;
-        }
-        r.aL = Ln;
-        r.aS = d;
-        const uint32_t tl = rd(pos - 2) & 3;
-        if (tl) {
-            r.bL = tl;
-            r.bS = kLitF | pos;
-            pos += tl;
-            r.st = ST_C;
-        } else
-            r.st = ST_A;
-        r.pos = pos;
-    }
-done:
-    {
-        const uint32_t need = far > r.pos ? far : r.pos;
-        if (need > k.z || r.pos < pos || capped)
-            r.fl = TK_BAD;                       // runs past the input (INPUT_OVERRUN), or a capped zero run
-        else if ((r.fl & TK_EOF) && r.pos != k.z)
-            r.fl = TK_BAD;                       // EOF not at the end (INPUT_NOT_CONSUMED)
-    }
-    return r;
+    return lzo1x_decode_general([&](uint32_t p) { return p < k.z ? in_byte(L, k, p) : 0u; },
+                                WinZeroRun{k, spec, spec ? kLzoZerosWinSpec : kLzoZerosWinTrue}, pos, st, k.z);
 }
 
-// Branch-free form for the common case: the instruction's fields lie in its
-// first 4 bytes (no 255-chunk length extension) inside the staged piece.
-// One zin round trip.
-__device__ __forceinline__ Tok tok(const WinLds& L, const Piece& k, uint32_t pos, uint32_t st, bool spec = false)
+// One instruction at (pos, st): the branch-free form (lzo1x_decode_word) when
+// its first 4 bytes lie inside the staged piece -- one zin round trip -- else
+// tok_slow.
+__device__ __forceinline__ Lzo1xIns tok(const WinLds& L, const Piece& k, uint32_t pos, uint32_t st, bool spec = false)
 {
     const uint32_t off = k.zb + (pos - k.I);
     const uint32_t lo = __builtin_amdgcn_alignbyte(L.zin[(off >> 2) + 1], L.zin[off >> 2], off & 3u);
-    const uint32_t t = lo & 0xFFu, b1 = __builtin_amdgcn_ubfe(lo, 8, 8);
-    const bool flit = st == ST_F && t > 17;
-    const uint32_t se = st == ST_F ? ST_A : st;
-    const bool lit = !flit && se == ST_A && t < 16;
-    const bool m1 = !flit && !lit && t < 16;
-    const bool m2 = !flit && t >= 64;
-    const bool m3 = !flit && t >= 32 && t < 64;
-    const bool m4 = !flit && t >= 16 && t < 32;
-    const bool ext = (lit && t == 0) || (m3 && (t & 31) == 0) || (m4 && (t & 7) == 0);
-    if (__builtin_expect((ext && b1 == 0) || pos + 4 > k.sEnd, 0))
+    bool general;
+    const Lzo1xIns r = lzo1x_decode_word<true>(lo, pos, st, k.z, general);
+    if (__builtin_expect(general || pos + 4 > k.sEnd, 0))
         return tok_slow(L, k, pos, st, spec);
-    const uint32_t e = ext ? 1u : 0u;
-    const uint32_t o16 = __builtin_amdgcn_ubfe(lo, 8u + 8u * e, 16);
-    const uint32_t dd4 = ((t & 8u) << 11) + (o16 >> 2);
-    const uint32_t used = (m1 || m2) ? 2u : 3u + e;
-    const uint32_t tl = __builtin_amdgcn_ubfe(lo, 8u * (used - 2u), 2);
-    const uint32_t nlit = flit ? t - 17 : (ext ? 15u + b1 : t) + 3u;
-    const uint32_t Ln = m1 ? (se == ST_B ? 3u : 2u)
-                      : m2 ? (t >> 5) + 1u
-                      : m3 ? (ext ? 31u + b1 : (t & 31u)) + 2u
-                           : (ext ? 7u + b1 : (t & 7u)) + 2u;
-    const uint32_t d = m1 ? (se == ST_B ? 0x801u : 1u) + (t >> 2) + (b1 << 2)
-                     : m2 ? 1u + ((t >> 2) & 7u) + (b1 << 3)
-                     : m3 ? 1u + (o16 >> 2) : dd4 + 0x4000u;
-    const bool eof = m4 && dd4 == 0;
-    const bool islit = flit || lit;
-    const uint32_t hdr = flit ? 1u : 1u + e;
-    Tok r;
-    r.aL = eof ? 0u : islit ? nlit : Ln;
-    r.aS = islit ? kLitF | (pos + hdr) : d;
-    r.bL = (islit || eof) ? 0u : tl;
-    r.bS = kLitF | (pos + used);
-    r.pos = islit ? pos + hdr + nlit : pos + used + (eof ? 0u : tl);
-    r.st = islit ? (flit && nlit < 4 ? ST_C : ST_B) : (tl && !eof ? ST_C : ST_A);
-    // the instruction (header, then literals) ends at r.pos
-    r.fl = r.pos > k.z ? TK_BAD : eof ? (r.pos != k.z ? TK_BAD : TK_EOF) : 0u;
     return r;
 }
+
+// TK_* of an instruction: refused, or the EOF marker at the end of the input
+__device__ __forceinline__ uint32_t tk_fl(const Lzo1xIns& t) { return t.bad ? TK_BAD : t.eof ? TK_EOF : 0u; }
 
 __device__ __forceinline__ uint32_t pack_pt(const Piece& k, uint32_t pos, uint32_t st) { return ((pos - k.I) << 2) | st; }
 
@@ -377,9 +235,9 @@ __device__ PieceOut parse_piece(WinLds& L, const Blk& blk, uint32_t I, uint32_t 
             uint32_t st = j ? (uint32_t)ST_A : st_in;
             uint32_t restart = pos;
             while (pos < b) {
-                const Tok t = tok(L, k, pos, st, j != 0);   // (lane 0 starts at the true entry)
-                if (t.fl) {
-                    if (j == 0 || (t.fl & TK_EOF))
+                const Lzo1xIns t = tok(L, k, pos, st, j != 0);   // (lane 0 starts at the true entry)
+                if (tk_fl(t)) {
+                    if (j == 0 || (tk_fl(t) & TK_EOF))
                         break;                   // stop point
                     restart++;                   // impossible guess: start one byte later
                     pos = restart;
@@ -454,9 +312,9 @@ __device__ PieceOut parse_piece(WinLds& L, const Blk& blk, uint32_t I, uint32_t 
                 if (j == f) {                    // walk from the true entry
                     uint32_t pos = cpos, st = cur & 3u;
                     for (;;) {
-                        const Tok t = tok(L, k, pos, st);
+                        const Lzo1xIns t = tok(L, k, pos, st);
                         nwt++;
-                        if (t.fl) {
+                        if (tk_fl(t)) {
                             w = pack_pt(k, pos, st);
                             break;
                         }
@@ -493,9 +351,9 @@ __device__ PieceOut parse_piece(WinLds& L, const Blk& blk, uint32_t I, uint32_t 
             uint32_t pos = I + (ent >> 2), st = ent & 3u;
             if (pos >= a) {
                 while (pos < b) {
-                    const Tok t = tok(L, k, pos, st);
-                    if (t.fl) {
-                        skind = t.fl;
+                    const Lzo1xIns t = tok(L, k, pos, st);
+                    if (tk_fl(t)) {
+                        skind = tk_fl(t);
                         spos = pos;
                         sst = st;
                         break;
@@ -517,7 +375,7 @@ __device__ PieceOut parse_piece(WinLds& L, const Blk& blk, uint32_t I, uint32_t 
         // literal source: a zin offset when the bytes are staged, else the input
         // position (long literal runs past the piece are read from HBM)
         auto lit_src = [&](uint32_t q, uint32_t n) -> uint32_t {
-            return q + n <= k.sEnd ? kLitF | (k.zb + (q - I)) : kLitF | kLitG | q;
+            return q + n <= k.sEnd ? kLzoLit | (k.zb + (q - I)) : kLzoLit | kLitG | q;
         };
         // P4: emit ops; at the op cap the instruction that does not fit starts
         // the next piece
@@ -528,8 +386,8 @@ __device__ PieceOut parse_piece(WinLds& L, const Blk& blk, uint32_t I, uint32_t 
             uint32_t pos = I + (ent >> 2), st = ent & 3u;
             uint32_t n = b_ops, outp = E + b_bytes;
             while (pos < b) {
-                const Tok t = tok(L, k, pos, st);
-                if (t.fl)
+                const Lzo1xIns t = tok(L, k, pos, st);
+                if (tk_fl(t))
                     break;
                 const uint32_t need = (t.aL ? 1u : 0u) + (t.bL ? 1u : 0u);
                 if (n + need > avail) {
@@ -541,13 +399,13 @@ __device__ PieceOut parse_piece(WinLds& L, const Blk& blk, uint32_t I, uint32_t 
                 }
                 if (t.aL) {
                     L.opp[nops + n] = outp;
-                    L.ops[nops + n] = (t.aS & kLitF) ? lit_src(t.aS & ~kLitF, t.aL) : t.aS;
+                    L.ops[nops + n] = (t.aS & kLzoLit) ? lit_src(t.aS & ~kLzoLit, t.aL) : t.aS;
                     n++;
                     outp += t.aL;
                 }
                 if (t.bL) {
                     L.opp[nops + n] = outp;
-                    L.ops[nops + n] = lit_src(t.bS & ~kLitF, t.bL);
+                    L.ops[nops + n] = lit_src(t.bS & ~kLzoLit, t.bL);
                     n++;
                     outp += t.bL;
                 }
@@ -669,7 +527,7 @@ __device__ bool run_window(WinLds& L, const Blk& blk, uint32_t S, uint32_t Ew, u
     for (uint32_t i = 0; i < 8; i++) {
         const uint32_t x = x0 + i;
         const bool valid = x >= S && x < Ew;
-        const bool lit = valid && (sv[i] & kLitF) != 0;
+        const bool lit = valid && (sv[i] & kLzoLit) != 0;
         lmask |= lit ? 1u << i : 0u;
         gmask |= lit && (sv[i] & kLitG) ? 1u << i : 0u;
         const uint32_t zoff = (sv[i] & 0xFFFFu) + (x - pv[i]);        // (garbage unless a zin literal)
@@ -823,7 +681,7 @@ __device__ void close_block(uint32_t b, bool ok, uint32_t len, uint32_t* out_len
         status[b] = 0;
     } else {
         out_len[b] = 0xFA110000u;
-        status[b] = kFallback;
+        status[b] = LZO_MI355X_DEC_PENDING;
         const uint32_t at = atomicAdd(&fallback[0], 1u);
         fallback_ids[at] = b;
     }

@@ -1513,7 +1513,7 @@ static void sc_run_group(struct sc_req **g, int k, struct sc_queue *q)
     if (kind != SC_COMPRESS) {
         int handed = 0;
         for (int i = 0; i < k; i++)
-            handed |= hh.status[i] == 0x7FFF0001;       /* (the throughput decoders' "exact decoder pending") */
+            handed |= hh.status[i] == LZO_MI355X_DEC_PENDING;
         if (handed &&
             (lzo_mi355x_launch_decompress_exact(d, dh.src_off, dh.src_len, out, dh.dst_off, dh.dst_cap,
                                                 olen, ost, dh.fb, dh.fb + 1, (uint32_t)k, (uint32_t)k,

@@ -13,6 +13,8 @@ extern "C" {
 
 /* status of a block lzo1x_encode_fast_kernel left to the general encoder */
 #define LZO_MI355X_ENC_PENDING 0x7FFF0002
+/* status of a block a speculative decoder (fast, win, lat) handed to the exact decoder */
+#define LZO_MI355X_DEC_PENDING 0x7FFF0001
 
 #define LZO_MI355X_FAST_MAX_N (1u << 24)   /* the throughput encoder's largest block (kMaxN) */
 
@@ -57,7 +59,7 @@ int lzo_mi355x_launch_decompress_concat(const uint8_t *src, const uint64_t *src_
 
 /* Throughput decoder (lzo1x_decode_fast.hip).  Blocks it does not finish
  * exactly are appended to fallback_ids[] (*fallback = count, must be 0 on
- * entry) and get status 0x7FFF0001 until the exact decoder runs on them.
+ * entry) and get status LZO_MI355X_DEC_PENDING until the exact decoder runs on them.
  * ops: nsets op-slot sets of lzo_mi355x_fast_ops_bytes_per_block() bytes,
  * shared by the workgroups through a pool (pool: LZO_MI355X_FAST_POOL_BYTES
  * of counters, ring: nsets u64, all zero on entry); nsets = min(nblocks,

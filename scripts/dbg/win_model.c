@@ -32,7 +32,7 @@ typedef struct {
     long windows, chase_iters, pieces, flushes, walks_fix;
 } M;
 
-/* ---- token decode (mirrors decode_one of lzo1x_decode_fast.hip) ---------- */
+/* ---- token decode (a copy of the general form that now lives in lzo1x_grammar.h) -- */
 typedef struct { uint32_t pos, st, aL, aS, bL, bS; int eof, bad, cut; } Tok;
 
 static uint32_t zb(const M *m, uint32_t I, uint32_t pos, int *oob)
