@@ -68,7 +68,12 @@ size_t lzo_mi355x_compress_scratch(uint32_t nblocks);
  * decoder: malformed streams, capacity or look-behind errors, destinations not
  * 16-byte aligned (the windowed decoder, which small batches take, needs only
  * 8), empty or >= 16 MiB inputs.  Every valid stream with a 16-byte aligned
- * destination stays on the throughput decoders. */
+ * destination stays on the throughput decoders.  (The latency decoder, which
+ * the single calls and host-resident chunks of at most 8 blocks take, has one
+ * limit more: it hands over a stream in which one length extension has 64 or
+ * more zero bytes -- a literal run from 16,339 bytes, an M3 match from 16,354,
+ * an M4 match from 16,330 -- since each of its threads would scan the run; the
+ * exact decoder behind it decodes such a stream in linear time.) */
 int lzo_mi355x_decompress_dev(const uint8_t *src, const uint64_t *src_off,
                               const uint32_t *src_len, uint8_t *dst,
                               const uint64_t *dst_off, const uint32_t *dst_cap,

@@ -324,3 +324,74 @@ def gpu_decompress_fast_alone(torch, src, dst, dev):
     nfb = int(head[0].item())
     return (olen.cpu().numpy().view(np.uint32).tolist(), st.cpu().numpy().tolist(),
             sorted(ids[:nfb].cpu().numpy().tolist()))
+
+
+# ---------------------------------------------------------------------------
+# The decoder paths on guarded batches (test_gpu_buffers.py, test_gpu_directed.py)
+# ---------------------------------------------------------------------------
+HANDED = 0x7FFF0001          # status of a block a throughput decoder handed over
+FILL = 0x5A                  # destination guard byte (decoders)
+FILL_ENC = 0xA5              # destination guard byte (encoders)
+OK, E_INPUT_OVERRUN, E_OUTPUT_OVERRUN = 0, -4, -5
+E_EOF_NOT_FOUND, E_INPUT_NOT_CONSUMED = -7, -8
+
+PATHS = ["exact", "win+exact", "fast+exact", "win", "fast", "lat1", "lat8"]
+
+
+def run_path(torch, path, dev, debug_env, comps, caps, src, dst):
+    """One launch of `path` on the caller's batches -> out_len, status, the
+    sorted ids a stand-alone throughput decoder handed over (None for the
+    paths with the exact decoder behind them) and the fallback count at
+    scratch byte 0 (None without scratch).  debug_env(value): sets
+    POM_LZO_DEBUG and has the library re-read it."""
+    if path in ("exact", "win+exact", "fast+exact"):
+        if path != "exact":
+            debug_env("decoder=" + path.split("+")[0])
+        olen, st, fb = gpu_decompress_dev(torch, src, dst, dev, scratch=path != "exact")
+        return olen, st, None, fb
+    if path == "win":
+        _, st, handed = gpu_decompress_win(torch, comps, caps, dev, src=src, dst=dst)
+        return dst.out_len, st, handed, None
+    if path == "fast":
+        olen, st, handed = gpu_decompress_fast_alone(torch, src, dst, dev)
+        return olen, st, handed, None
+    _, st, handed = gpu_decompress_lat(torch, comps, caps, dev, group=int(path[3:]), src=src, dst=dst)
+    return dst.out_len, st, handed, None
+
+
+def check_decoded(names, want, caps, olen, st, handed, dst):
+    """The oracle rule and the guard rule.  With the exact decoder behind
+    (handed is None): status, out_len and bytes equal the oracle's.  A
+    stand-alone throughput decoder reports OK only where the oracle does, then
+    with its bytes; anything else is handed over (status HANDED, the id in
+    the list; None: a block the latency decoder's launcher does not take).
+    Guards: a finished block wrote min(out_len, cap) bytes, a handed-over one
+    at most its room."""
+    alone = handed is not None
+    n = len(want)
+    written = [int(caps[i]) if alone and st[i] != OK else min(int(olen[i]), int(caps[i]))
+               for i in range(n)]
+    problems = []
+    try:
+        arena = assert_guards(dst, written, FILL)
+    except AssertionError as e:
+        problems.append(str(e))
+        arena = dst.arena.cpu().numpy()
+    off = dst.host_off
+    hset = set(handed or [])
+    bad = []
+    for i, (rc, ref) in enumerate(want):
+        got = arena[int(off[i]): int(off[i]) + written[i]].tobytes()
+        if not alone or st[i] == OK:
+            good = (st[i], int(olen[i]), got) == (rc, len(ref), ref)
+        else:
+            good = st[i] is None or (st[i] == HANDED and i in hset)
+        if not good:
+            bad.append((names[i], st[i], rc, int(olen[i]), len(ref)))
+    if bad:
+        problems.append(f"{len(bad)} of {n} blocks wrong (name, status, oracle's, out_len, oracle's): {bad[:6]}")
+    if alone and sorted(hset) != [i for i in range(n) if st[i] == HANDED]:
+        problems.append("the fallback list is not the blocks with status HANDED")
+    print(f"{n} blocks: {sum(s == OK for s in st)} OK, {sum(s == HANDED for s in st)} handed over, "
+          f"{sum(s is None for s in st)} not launched, {sum(rc == OK for rc, _ in want)} OK by the oracle")
+    assert not problems, "\n".join(problems)

@@ -21,19 +21,14 @@ import ctypes
 import numpy as np
 import pytest
 
+from gpu_util import (E_EOF_NOT_FOUND, E_INPUT_NOT_CONSUMED, E_INPUT_OVERRUN, E_OUTPUT_OVERRUN, FILL,
+                      FILL_ENC, OK, PATHS, check_decoded, run_path)
 from pomegranate_amd import lzo, synth
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-HANDED = 0x7FFF0001          # status of a block a throughput decoder handed over
-FILL = 0x5A                  # destination guard byte (decoders)
-FILL_ENC = 0xA5              # destination guard byte (encoders)
-OK, E_INPUT_OVERRUN, E_OUTPUT_OVERRUN = 0, -4, -5
-E_EOF_NOT_FOUND, E_INPUT_NOT_CONSUMED = -7, -8
-
-PATHS = ["exact", "win+exact", "fast+exact", "win", "fast", "lat1", "lat8"]
 MODES = ["zero", "ff", "random", "continuation"]
 
 
@@ -263,64 +258,8 @@ def concat_cases(oracle, columns):
 
 
 # ---------------------------------------------------------------------------
-# The decoder paths
+# The decoder paths: gpu_util.run_path, gpu_util.check_decoded
 # ---------------------------------------------------------------------------
-def run_path(path, dev, gu, debug_env, comps, caps, src, dst):
-    """One launch of `path` on the caller's batches -> out_len, status, the
-    sorted ids a stand-alone throughput decoder handed over (None for the
-    paths with the exact decoder behind them) and the fallback count at
-    scratch byte 0 (None without scratch)."""
-    if path in ("exact", "win+exact", "fast+exact"):
-        if path != "exact":
-            debug_env("decoder=" + path.split("+")[0])
-        olen, st, fb = gu.gpu_decompress_dev(torch, src, dst, dev, scratch=path != "exact")
-        return olen, st, None, fb
-    if path == "win":
-        _, st, handed = gu.gpu_decompress_win(torch, comps, caps, dev, src=src, dst=dst)
-        return dst.out_len, st, handed, None
-    if path == "fast":
-        olen, st, handed = gu.gpu_decompress_fast_alone(torch, src, dst, dev)
-        return olen, st, handed, None
-    _, st, handed = gu.gpu_decompress_lat(torch, comps, caps, dev, group=int(path[3:]), src=src, dst=dst)
-    return dst.out_len, st, handed, None
-
-
-def check_decoded(gu, names, want, caps, olen, st, handed, dst):
-    """The oracle rule and the guard rule.  With the exact decoder behind
-    (handed is None): status, out_len and bytes equal the oracle's.  A
-    stand-alone throughput decoder reports OK only where the oracle does, then
-    with its bytes; anything else is handed over (status HANDED, the id in
-    the list; None: a block the latency decoder's launcher does not take).
-    Guards: a finished block wrote min(out_len, cap) bytes, a handed-over one
-    at most its room."""
-    alone = handed is not None
-    n = len(want)
-    written = [int(caps[i]) if alone and st[i] != OK else min(int(olen[i]), int(caps[i]))
-               for i in range(n)]
-    problems = []
-    try:
-        arena = gu.assert_guards(dst, written, FILL)
-    except AssertionError as e:
-        problems.append(str(e))
-        arena = dst.arena.cpu().numpy()
-    off = dst.host_off
-    hset = set(handed or [])
-    bad = []
-    for i, (rc, ref) in enumerate(want):
-        got = arena[int(off[i]): int(off[i]) + written[i]].tobytes()
-        if not alone or st[i] == OK:
-            good = (st[i], int(olen[i]), got) == (rc, len(ref), ref)
-        else:
-            good = st[i] is None or (st[i] == HANDED and i in hset)
-        if not good:
-            bad.append((names[i], st[i], rc, int(olen[i]), len(ref)))
-    if bad:
-        problems.append(f"{len(bad)} of {n} blocks wrong (name, status, oracle's, out_len, oracle's): {bad[:6]}")
-    if alone and sorted(hset) != [i for i in range(n) if st[i] == HANDED]:
-        problems.append("the fallback list is not the blocks with status HANDED")
-    print(f"{n} blocks: {sum(s == OK for s in st)} OK, {sum(s == HANDED for s in st)} handed over, "
-          f"{sum(s is None for s in st)} not launched, {sum(rc == OK for rc, _ in want)} OK by the oracle")
-    assert not problems, "\n".join(problems)
 
 
 def long_extension(z):
@@ -353,8 +292,8 @@ def test_destination_alignment(dev, gu, debug_env, align_fx, path):
     src = gu.guarded_batch(torch, comps, dev, [(5 * i) % 16 for i in range(n)], 0, neighbours="ff")
     dst = gu.guarded_batch(torch, caps, dev, [i % 16 for i in range(n)], FILL)
     assert sorted(set((dst.host_off % 16).tolist())) == list(range(16))
-    olen, st, handed, fb = run_path(path, dev, gu, debug_env, comps, caps, src, dst)
-    check_decoded(gu, names, want, caps, olen, st, handed, dst)
+    olen, st, handed, fb = run_path(torch, path, dev, debug_env, comps, caps, src, dst)
+    check_decoded(names, want, caps, olen, st, handed, dst)
     off8 = [i for i in range(n) if dst.host_off[i] % 8]
     off16 = [i for i in range(n) if dst.host_off[i] % 16]
     if path == "exact":
@@ -393,8 +332,8 @@ def test_destination_capacity(dev, gu, debug_env, capacity_fx, path):
     n = len(comps)
     src = gu.guarded_batch(torch, comps, dev, [(3 * i) % 16 for i in range(n)], 0, neighbours="ff")
     dst = gu.guarded_batch(torch, caps, dev, [c[3] for c in capacity_fx], FILL)
-    olen, st, handed, _ = run_path(path, dev, gu, debug_env, comps, caps, src, dst)
-    check_decoded(gu, names, want, caps, olen, st, handed, dst)
+    olen, st, handed, _ = run_path(torch, path, dev, debug_env, comps, caps, src, dst)
+    check_decoded(names, want, caps, olen, st, handed, dst)
 
 
 # ---------------------------------------------------------------------------
@@ -424,8 +363,8 @@ def test_source_bounds(dev, gu, debug_env, prefix_fx, path, mode):
     src = gu.guarded_batch(torch, comps, dev, [i % 16 for i in range(n)], 0, neighbours=mode,
                            continuation=[c[3] for c in cases] if mode == "continuation" else None)
     dst = gu.guarded_batch(torch, caps, dev, [0] * n, FILL)
-    olen, st, handed, _ = run_path(path, dev, gu, debug_env, comps, caps, src, dst)
-    check_decoded(gu, names, want, caps, olen, st, handed, dst)
+    olen, st, handed, _ = run_path(torch, path, dev, debug_env, comps, caps, src, dst)
+    check_decoded(names, want, caps, olen, st, handed, dst)
     # identical across the neighbourhoods (handed-over blocks: their status)
     mine = [(s, o if s == OK else None) for s, o in zip(st, olen)] if handed is not None else list(zip(st, olen))
     first_mode, first = prefix_fx["seen"].setdefault(path, (mode, mine))
@@ -564,5 +503,5 @@ def test_concat_streams(dev, gu, concat_fx, mode):
     assert fn(p(src.arena), p(src.off), p(src.length), p(dst.arena), p(dst.off), p(dst.length),
               p(olen), p(st), n, torch.cuda.current_stream().cuda_stream) == 0
     torch.cuda.synchronize()
-    check_decoded(gu, names, want, caps, olen.cpu().numpy().view(np.uint32).tolist(),
+    check_decoded(names, want, caps, olen.cpu().numpy().view(np.uint32).tolist(),
                   st.cpu().numpy().tolist(), None, dst)
