@@ -26,6 +26,7 @@
 #include "lzo_mi355x.h"
 #include "lzo_mi355x_kernels.h"
 #include "minilzo.h"
+#include "pom_gc.h"
 
 /* Debug and experiment switches: ONE environment variable, POM_LZO_DEBUG,
  * a comma-separated list of key=value.  No product path
@@ -541,6 +542,9 @@ struct layout {
     size_t packed;
     size_t o_srcoff, o_dstoff, o_srclen, o_dstcap, o_outlen, o_status, o_poff;
     size_t o_src, o_dst, o_scr, o_pack, htotal, dtotal;
+    /* OP_GC_SCAN chunks (gc_layout_make) */
+    size_t nlzo, rcap;
+    size_t o_scanoff, o_first, o_live, o_nranges, o_err, o_adepth, o_hrng;
 };
 
 static void layout_make(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
@@ -608,7 +612,7 @@ static void layout_fill(const struct layout *L, uint8_t *h, const uint8_t *const
     }
 }
 
-enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT };
+enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN };
 
 /* One host batch: the caller's arrays, the capacities the kernels use, and
  * the plan (device split, largest-first order). */
@@ -631,6 +635,7 @@ struct hbatch {
     pom_chunk_fn on_chunk;  /* called with each delivered chunk's block ids, or NULL */
     pom_chunk_fn pre_chunk; /* called with a chunk's block ids before its inputs are staged */
     void *cb_ctx;
+    struct pom_gc_sink *gc; /* OP_GC_SCAN: the walk's per-block inputs and results */
 };
 
 /* debug key host_timing=1: per-batch and per-chunk wall times on stderr (diagnostic) */
@@ -887,6 +892,232 @@ static int chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *
     return 0;
 }
 
+/* ------------------------------------------------------------------------ */
+/* OP_GC_SCAN chunks: decode, walk (itb_scan.hip), counts and ranges back    */
+/* ------------------------------------------------------------------------ */
+/* A chunk's blocks are its LZO records first (the decoders run over that
+ * prefix alone), then the records stored uncompressed, which are walked where
+ * they are staged.  Staging (host and device alike up to the inputs' end):
+ *   [src_off u64][dst_off u64][scan_off u64][first u64, nb + 1][src_len u32][dst_cap u32]
+ *   [status i32][out_len u32][live u32][nranges u32][err i32]   <- D2H, one copy
+ *   [adepth u8]
+ *   [src bytes, 16-B aligned per block]
+ *   host:   [the chunk's ranges]                                 <- D2H, sized after the first
+ *   device: [decoded payloads][decoder scratch][ranges, room for every ITE the payloads can hold]
+ * No decoded byte leaves the device. */
+struct pom_gc_buf {
+    struct pom_gc_buf *next;
+    uint64_t pad;
+    struct pom_gc_range r[];
+};
+
+/* The ranges a payload of n bytes can yield: one per whole ITE. */
+static size_t gc_max_ranges(size_t n)
+{
+    const size_t ites = n > POM_ITB_ITE_OFF ? (n - POM_ITB_ITE_OFF) / POM_ITE_SIZE : 0;
+    return ites < 1024 ? ites : 1024;
+}
+
+/* ids[0, nb): the LZO blocks to the front (any order inside either part).
+ * Returns how many there are. */
+static size_t gc_partition(size_t *ids, size_t nb, const uint8_t *is_lzo)
+{
+    size_t lo = 0, hi = nb;
+    while (lo < hi) {
+        if (is_lzo[ids[lo]]) {
+            lo++;
+        } else {
+            const size_t t = ids[lo];
+            ids[lo] = ids[--hi];
+            ids[hi] = t;
+        }
+    }
+    return lo;
+}
+
+static void gc_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo,
+                           const size_t *src_len, const size_t *cap)
+{
+    memset(L, 0, sizeof(*L));
+    L->nb = nb;
+    L->ids = ids;
+    L->nlzo = nlzo;
+    size_t o = 0;
+    L->o_srcoff = o; o += 8 * nb;
+    L->o_dstoff = o; o += 8 * nb;
+    L->o_scanoff = o; o += 8 * nb;
+    L->o_first = o; o += 8 * (nb + 1);
+    L->o_srclen = o; o += 4 * nb;
+    L->o_dstcap = o; o += 4 * nb;
+    L->o_status = o; o += 4 * nb;
+    L->o_outlen = o; o += 4 * nb;
+    L->o_live = o; o += 4 * nb;
+    L->o_nranges = o; o += 4 * nb;
+    L->o_err = o; o += 4 * nb;
+    L->o_adepth = o; o += nb;
+    o = ALIGN_UP(o, 256);
+    L->o_src = o;
+    size_t s = 0, d = 0, r = 0;
+    for (size_t i = 0; i < nb; i++) {
+        s += ALIGN_UP(src_len[ids[i]], 16);
+        if (i < nlzo)
+            d += ALIGN_UP(cap[ids[i]], 16);
+        r += gc_max_ranges(i < nlzo ? cap[ids[i]] : src_len[ids[i]]);
+    }
+    L->rcap = r;
+    o += ALIGN_UP(s, 256);
+    L->o_dst = o;
+    L->o_hrng = o;
+    L->htotal = o + sizeof(struct pom_gc_range) * r;
+    o += ALIGN_UP(d, 256);
+    L->o_scr = o;
+    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
+    L->o_pack = o;
+    L->dtotal = o + sizeof(struct pom_gc_range) * r;
+}
+
+static void gc_layout_fill(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    uint64_t *so = (uint64_t *)(h + L->o_srcoff);
+    uint64_t *dof = (uint64_t *)(h + L->o_dstoff);
+    uint64_t *sco = (uint64_t *)(h + L->o_scanoff);
+    uint32_t *sl = (uint32_t *)(h + L->o_srclen);
+    uint32_t *dc = (uint32_t *)(h + L->o_dstcap);
+    int32_t *st = (int32_t *)(h + L->o_status);
+    uint32_t *ol = (uint32_t *)(h + L->o_outlen);
+    uint8_t *ad = h + L->o_adepth;
+    size_t s = 0, d = 0;
+    struct copy_job *jobs = malloc(L->nb * sizeof(*jobs));
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        const int lzo = i < L->nlzo;
+        so[i] = s;
+        dof[i] = d;
+        sl[i] = (uint32_t)B->src_len[b];
+        dc[i] = lzo ? (uint32_t)B->cap[b] : 0;
+        /* the walk reads the decoders' status and out_len; a stored payload's are set here */
+        sco[i] = lzo ? L->o_dst + d : L->o_src + s;
+        st[i] = 0;
+        ol[i] = lzo ? 0 : (uint32_t)B->src_len[b];
+        ad[i] = B->gc->adepth[b];
+        if (jobs) {
+            jobs[i].dst = h + L->o_src + s;
+            jobs[i].src = B->src[b];
+            jobs[i].len = B->src_len[b];
+        } else if (B->src_len[b]) {
+            memcpy(h + L->o_src + s, B->src[b], B->src_len[b]);
+        }
+        s += ALIGN_UP(B->src_len[b], 16);
+        d += ALIGN_UP((size_t)dc[i], 16);
+    }
+    if (jobs) {
+        copy_jobs(jobs, L->nb);
+        free(jobs);
+    }
+}
+
+/* As chunk_launch: everything queued on the slot's stream, nothing waited for. */
+static int gc_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
+{
+    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
+        return -1;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    hipStream_t s = S->stream;
+    const uint32_t nb = (uint32_t)L->nb;
+    gc_layout_fill(L, h, B);
+    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
+        return -1;
+    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
+    int32_t *st = (int32_t *)(d + L->o_status);
+    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
+                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
+                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
+        lzo_mi355x_launch_gc_scan(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth, nb,
+                                  (uint32_t)B->gc->column, (uint32_t *)(d + L->o_live),
+                                  (uint32_t *)(d + L->o_nranges), (uint64_t *)(d + L->o_first),
+                                  (struct pom_gc_range *)(d + L->o_pack), L->rcap,
+                                  (int32_t *)(d + L->o_err), s) != 0)
+        return -1;
+    return hipMemcpyAsync(h + L->o_status, d + L->o_status, 20 * L->nb, hipMemcpyDeviceToHost, s) ==
+                   hipSuccess ? 0 : -1;
+}
+
+/* As chunk_collect: once the counts are back, the D2H of exactly the chunk's ranges. */
+static int gc_chunk_collect(struct slot *S, struct layout *L, int poll)
+{
+    if (L->collected)
+        return 1;
+    hipStream_t s = S->stream;
+    if (poll) {
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady)
+            return 0;
+        if (q != hipSuccess)
+            return -1;
+    } else if (hipStreamSynchronize(s) != hipSuccess) {
+        return -1;
+    }
+    const uint32_t *hnr = (const uint32_t *)(S->hmem + L->o_nranges);
+    size_t total = 0;
+    for (size_t i = 0; i < L->nb; i++)
+        total += hnr[i];
+    if (total > L->rcap)
+        return -1;
+    if (total && hipMemcpyAsync(S->hmem + L->o_hrng, S->dmem + L->o_pack, sizeof(struct pom_gc_range) * total,
+                                hipMemcpyDeviceToHost, s) != hipSuccess)
+        return -1;
+    L->packed = sizeof(struct pom_gc_range) * total;
+    L->collected = 1;
+    return 1;
+}
+
+/* As chunk_deliver: the chunk's ranges into a buffer of their own (the chunks
+ * reorder the blocks, so the caller places each block's ranges itself). */
+static int gc_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
+                            struct slot *nS, struct layout *nL)
+{
+    if (gc_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
+        return -1;
+    if (nS && gc_chunk_collect(nS, nL, 0) < 0)
+        return -1;
+    struct pom_gc_sink *G = B->gc;
+    const uint8_t *h = S->hmem;
+    const int32_t *hst = (const int32_t *)(h + L->o_status);
+    const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
+    const uint32_t *hlv = (const uint32_t *)(h + L->o_live);
+    const uint32_t *hnr = (const uint32_t *)(h + L->o_nranges);
+    const int32_t *her = (const int32_t *)(h + L->o_err);
+    struct pom_gc_buf *buf = malloc(sizeof(*buf) + L->packed);
+    if (!buf)
+        return -1;
+    memcpy(buf->r, h + L->o_hrng, L->packed);
+    size_t at = 0;
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        G->status[b] = hst[i];
+        G->out_len[b] = hol[i];
+        G->live[b] = hlv[i];
+        G->nranges[b] = hnr[i];
+        G->err[b] = her[i];
+        G->rng[b] = buf->r + at;
+        at += hnr[i];
+    }
+    pthread_mutex_lock(&G->mu);
+    buf->next = G->bufs;
+    G->bufs = buf;
+    pthread_mutex_unlock(&G->mu);
+    return 0;
+}
+
+void pom_gc_sink_free(struct pom_gc_sink *sink)
+{
+    while (sink->bufs) {
+        struct pom_gc_buf *next = sink->bufs->next;
+        free(sink->bufs);
+        sink->bufs = next;
+    }
+}
+
 /* A host batch is cut into chunks of at most kChunkBudget bytes of input plus
  * output capacity (a larger block is a chunk of its own), pipelined through
  * the device's kSlots slots: chunk k is staged and its copies and kernels are
@@ -951,6 +1182,16 @@ static int dev_run(void *arg, int d)
                 rev[i] = ids[nids - 1 - i];
             ids = rev;
         }
+        /* walk chunks put their LZO blocks first (gc_partition): in a copy of the ids */
+        const int gc = B->kind == OP_GC_SCAN;
+        if (gc && !rev) {
+            if ((rev = malloc(nids * sizeof(*rev))) != NULL) {
+                memcpy(rev, ids, nids * sizeof(*rev));
+                ids = rev;
+            } else {
+                rc = -1;
+            }
+        }
         struct layout L[kSlots];
         int live[kSlots] = {0};                /* slot holds a launched chunk */
         size_t from = 0;
@@ -984,7 +1225,8 @@ static int dev_run(void *arg, int d)
             if (dj >= 0) {
                 const int ahead = !B->ooo && live[nxt] && nxt != dj;
                 const int fail = fail_at >= 0 && ndeliv++ == fail_at;
-                if (fail || chunk_deliver(&c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL, &L[nxt]) != 0) {
+                if (fail || (gc ? gc_chunk_deliver : chunk_deliver)(&c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL,
+                                                                     &L[nxt]) != 0) {
                     rc = -1;
                     for (int j = 0; j < B->nslots; j++)
                         hipStreamSynchronize(c->s[j].stream);
@@ -1000,13 +1242,17 @@ static int dev_run(void *arg, int d)
             if (more) {
                 const size_t end = pom_chunk_end(ids, from, nids, B->cost,
                                                  k ? B->budget : B->budget / 4, kChunkBlocks);
-                layout_make(&L[cur], ids + from, end - from, B->src_len, B->cap,
-                            B->kind == OP_COMPRESS);
+                if (gc)
+                    gc_layout_make(&L[cur], ids + from, end - from,
+                                   gc_partition(rev + from, end - from, B->gc->is_lzo), B->src_len, B->cap);
+                else
+                    layout_make(&L[cur], ids + from, end - from, B->src_len, B->cap,
+                                B->kind == OP_COMPRESS);
                 /* the caller may produce the chunk's inputs now (e.g. read them),
                  * while the chunks in flight are copied and decoded */
                 if (B->pre_chunk)
                     B->pre_chunk(B->cb_ctx, ids + from, end - from);
-                if (chunk_launch(&c->s[cur], &L[cur], B) != 0) {
+                if ((gc ? gc_chunk_launch : chunk_launch)(&c->s[cur], &L[cur], B) != 0) {
                     rc = -1;
                     hipStreamSynchronize(c->s[cur].stream);
                 } else {
@@ -1065,12 +1311,13 @@ static int batch_devices(int *devs)
 
 static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                            uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
-                           pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx);
+                           pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
+                           struct pom_gc_sink *gc);
 
 static int batch_common(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                         uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks)
 {
-    return batch_common_cb(kind, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL);
+    return batch_common_cb(kind, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL, NULL);
 }
 
 /* lzo_mi355x_decompress_batch with pre_chunk(ctx, ids, nb) called before each
@@ -1081,7 +1328,7 @@ int pom_decompress_batch_chunked(const uint8_t *const *src, const size_t *src_le
                                  size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn pre_chunk,
                                  void *ctx)
 {
-    return batch_common_cb(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx);
+    return batch_common_cb(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx, NULL);
 }
 
 /* lzo_mi355x_compress_batch with on_chunk(ctx, ids, nb) called as each chunk's
@@ -1092,12 +1339,13 @@ int pom_compress_batch_chunked(const uint8_t *const *src, const size_t *src_len,
                                size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn on_chunk,
                                void *ctx)
 {
-    return batch_common_cb(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx);
+    return batch_common_cb(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx, NULL);
 }
 
 static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                            uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
-                           pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx)
+                           pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
+                           struct pom_gc_sink *gc)
 {
     const double t0 = g_timing ? now_ms() : 0;
     struct tctx *t = tctx_get();
@@ -1124,14 +1372,14 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
             free(cost);
             return LZO_E_ERROR;
         }
-        cap[b] = kind == OP_COMPRESS ? lzo_mi355x_worst_compress(src_len[b]) : dst_len[b];
+        cap[b] = kind == OP_COMPRESS ? lzo_mi355x_worst_compress(src_len[b]) : gc ? gc->cap[b] : dst_len[b];
         if (cap[b] > 0xFFFFFFF0u)
             cap[b] = 0xFFFFFFF0u;
         cost[b] = src_len[b] + cap[b];
     }
     struct hbatch B = {kind, src, src_len, dst, dst_len, status, cap, cost,
                        kind == OP_COMPRESS ? kChunkBudgetCompress : kChunkBudget,
-                       {0, 1, NULL, NULL}, devs, t, 0, kSlots, 0, on_chunk, pre_chunk, cb_ctx};
+                       {0, 1, NULL, NULL}, devs, t, 0, kSlots, 0, on_chunk, pre_chunk, cb_ctx, gc};
     B.ooo = kind == OP_COMPRESS && pom_dbg_int("ooo", 1) != 0;
     /* compress chunks that fit the LDS encoder's 4 blocks per CU at once use
      * it: a block alone on its CU finishes twice as fast as with the
@@ -1148,18 +1396,31 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
         /* blocks a failed device leaves untouched read as errors */
         for (size_t b = 0; b < nblocks; b++) {
             status[b] = LZO_E_ERROR;
-            dst_len[b] = 0;
+            if (gc)
+                gc->err[b] = LZO_E_ERROR;
+            else
+                dst_len[b] = 0;
         }
         rc = pom_run_devices(B.plan.ndev, dev_run, &B) == 0 ? LZO_E_OK : LZO_E_ERROR;
         if (g_timing)
             fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n",
-                    kind == OP_COMPRESS ? "compress" : "decompress", nblocks, B.plan.ndev,
+                    kind == OP_COMPRESS ? "compress" : gc ? "gc scan" : "decompress", nblocks, B.plan.ndev,
                     now_ms() - t0);
         pom_plan_free(&B.plan);
     }
     free(cap);
     free(cost);
     return rc;
+}
+
+int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                        struct pom_gc_sink *sink)
+{
+    for (size_t b = 0; b < nblocks; b++) {
+        sink->out_len[b] = sink->live[b] = sink->nranges[b] = 0;
+        sink->rng[b] = NULL;
+    }
+    return batch_common_cb(OP_GC_SCAN, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink);
 }
 
 int lzo_mi355x_compress_batch(const uint8_t *const *src, const size_t *src_len,

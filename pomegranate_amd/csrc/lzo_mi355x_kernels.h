@@ -3,6 +3,7 @@
 #ifndef POM_LZO_MI355X_KERNELS_H
 #define POM_LZO_MI355X_KERNELS_H 1
 
+#include <pthread.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <hip/hip_runtime_api.h>
@@ -154,6 +155,40 @@ void pom_copy_parallel(uint8_t *const *dst, const uint8_t *const *src, const siz
 int lzo_mi355x_launch_pack(const uint8_t *from, const uint64_t *from_off, const uint32_t *len,
                            const uint32_t *cap, const uint64_t *to_off, uint8_t *to,
                            uint32_t nblocks, hipStream_t stream);
+
+/* The garbage collector's ITB walk (itb_scan.hip): pom_gc_scan_dev of
+ * include/pom_gc.h, three launches on `stream`. */
+struct pom_gc_range;
+int lzo_mi355x_launch_gc_scan(const uint8_t *payload, const uint64_t *payload_off,
+                              const uint32_t *payload_len, const int32_t *status,
+                              const uint8_t *adepth, uint32_t nitb, uint32_t column,
+                              uint32_t *live, uint32_t *nranges, uint64_t *first,
+                              struct pom_gc_range *ranges, uint64_t ranges_cap, int32_t *err,
+                              hipStream_t stream);
+
+/* Host side (lzo_host.c), not part of the ABI: the chunk pipeline of the host
+ * batches with the walk queued behind each chunk's decode (gc_scan.c).  Block
+ * b is src_len[b] bytes at src[b]: an LZO1X stream decoded on the GPU with
+ * capacity cap[b] when is_lzo[b], else a payload walked as staged.  Per block
+ * the decoder's status and out_len (0 and src_len[b] when not is_lzo), and
+ * live, nranges and err as pom_gc_scan_dev; rng[b] = the block's nranges[b]
+ * ranges, inside one of the per-chunk buffers linked at bufs (the caller
+ * frees them with pom_gc_sink_free).  No decoded byte is copied back. */
+struct pom_gc_buf;
+struct pom_gc_sink {
+    const uint8_t *is_lzo;
+    const size_t *cap;
+    const uint8_t *adepth;
+    int column;
+    int32_t *status, *err;
+    uint32_t *out_len, *live, *nranges;
+    const struct pom_gc_range **rng;
+    struct pom_gc_buf *bufs;
+    pthread_mutex_t mu;             /* bufs: chunks of a multi-GPU batch finish on several threads */
+};
+int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                        struct pom_gc_sink *sink);
+void pom_gc_sink_free(struct pom_gc_sink *sink);
 
 #ifdef __cplusplus
 }

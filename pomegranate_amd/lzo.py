@@ -60,6 +60,8 @@ EXPORTS = (
     # include/pom_xnet.h
     "pom_xnet_frame", "pom_xnet_parse", "pom_xnet_itb_reply_batch", "pom_xnet_itb_wb_batch",
     "pom_xnet_itb_recv_batch",
+    # include/pom_gc.h
+    "pom_gc_scan_dev", "pom_gc_scan_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
