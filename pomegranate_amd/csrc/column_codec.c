@@ -1,12 +1,17 @@
 /*
  * column_codec.c -- the client column-data codec (include/pom_column.h) over
  * the host-resident LZO1X batch API.  Format and fallback follow
- * api/api.c:6509-6541, :6652-6689 and :6427-6446.
+ * api/api.c:6509-6541, :6652-6689 and :6427-6446; reads by offset and size
+ * (:6447-6460) go through the host batches' pipeline with the region copy
+ * behind each chunk's decode (lzo_host.c, OP_COL_READ; the rules are
+ * col_slice.h's).
  */
 #include <stdlib.h>
 #include <string.h>
 
+#include "col_slice.h"
 #include "lzo_mi355x.h"
+#include "lzo_mi355x_kernels.h"
 #include "minilzo.h"
 #include "pom_column.h"
 
@@ -168,5 +173,126 @@ out:
     free(mdst);
     free(mdlen);
     free(mst);
+    return rc;
+}
+
+int pom_col_slice_dev(const uint8_t *data, const uint64_t *data_off, const uint32_t *data_len,
+                      const int32_t *status, const uint64_t *want, uint32_t ncol,
+                      const struct pom_col_req *req, uint32_t nreq,
+                      uint8_t *out, const uint64_t *out_off,
+                      uint32_t *out_len, int32_t *err, void *stream)
+{
+    return lzo_mi355x_launch_col_slice(data, data_off, data_len, status, want, ncol, req, nreq, out, out_off,
+                                       out_len, err, (hipStream_t)stream);
+}
+
+/* The columns some request names and that pass the header checks go to the
+ * GPU, k = 0 ... m - 1: column idx[k], with its requests gathered behind
+ * first[k].  The requests of the others are decided here.  The columns whose
+ * first stream ends short of the input are then read again as consecutive
+ * streams (see pom_col_unzip_batch). */
+int pom_col_read_batch(const uint8_t *const *zip, const size_t *zip_len, size_t ncol,
+                       const struct pom_col_req *req, size_t nreq,
+                       uint8_t *const *out, size_t *out_len, int *err)
+{
+    if (lzo_mi355x_device_count() <= 0)
+        return LZO_E_ERROR;
+    if (nreq == 0)
+        return LZO_E_OK;
+    size_t *slot = malloc((ncol + 1) * sizeof(*slot));       /* column -> k, or a code below */
+    size_t *first = calloc(ncol + 2, sizeof(*first));
+    size_t *fill = malloc((ncol + 1) * sizeof(*fill));
+    size_t *ids = malloc(nreq * sizeof(*ids));
+    const uint8_t **src = malloc((ncol + 1) * sizeof(*src));
+    size_t *slen = malloc((ncol + 1) * sizeof(*slen));
+    uint64_t *want = malloc((ncol + 1) * sizeof(*want));
+    int32_t *st = malloc((ncol + 1) * sizeof(*st));
+    int rc = LZO_E_OUT_OF_MEMORY;
+    if (!slot || !first || !fill || !ids || !src || !slen || !want || !st)
+        goto out;
+    const size_t kUnused = (size_t)-1, kNoHeader = (size_t)-2, kRefused = (size_t)-3;
+    for (size_t c = 0; c < ncol; c++)
+        slot[c] = kUnused;
+    size_t m = 0;
+    for (size_t r = 0; r < nreq; r++) {
+        const size_t c = req[r].col;
+        out_len[r] = 0;
+        if (c >= ncol || slot[c] != kUnused)
+            continue;
+        uint64_t w = 0;
+        if (zip_len[c] >= POM_COL_HDR)
+            memcpy(&w, zip[c], POM_COL_HDR);
+        if (zip_len[c] < POM_COL_HDR) {
+            slot[c] = kNoHeader;
+        } else if (!col_slice_want_ok(w, zip_len[c] - POM_COL_HDR)) {
+            slot[c] = kRefused;                 /* nothing is staged for a length the stream cannot yield */
+        } else {
+            slot[c] = m;
+            src[m] = zip[c] + POM_COL_HDR;
+            slen[m] = zip_len[c] - POM_COL_HDR;
+            want[m] = w;
+            m++;
+        }
+    }
+    size_t ngpu = 0;
+    for (size_t r = 0; r < nreq; r++) {
+        const size_t c = req[r].col;
+        if (c < ncol && slot[c] < m) {
+            first[slot[c] + 1]++;
+            err[r] = LZO_E_ERROR;               /* until its chunk delivers */
+            ngpu++;
+        } else {
+            uint64_t n;
+            err[r] = col_slice_decide(c < ncol, c < ncol && slot[c] != kNoHeader, LZO_E_ERROR, 0, 0,
+                                      req[r].offset, req[r].size, &n);
+        }
+    }
+    rc = LZO_E_OK;
+    if (ngpu == 0)
+        goto out;
+    for (size_t k = 0; k < m; k++) {
+        first[k + 1] += first[k];
+        fill[k] = first[k];
+    }
+    for (size_t r = 0; r < nreq; r++) {
+        const size_t c = req[r].col;
+        if (c < ncol && slot[c] < m)
+            ids[fill[slot[c]]++] = r;
+    }
+    struct pom_col_sink C = {want, first, ids, req, out, out_len, err, st, 0};
+    rc = pom_col_read_chunked(src, slen, m, &C);
+    if (rc != LZO_E_OK)
+        goto out;
+    /* the reference hvfs_fwritev layout: those columns again, with their requests */
+    size_t nm = 0, nmr = 0;
+    for (size_t k = 0; k < m; k++)
+        if (st[k] == LZO_E_INPUT_NOT_CONSUMED) {
+            const size_t nr = first[k + 1] - first[k];
+            memmove(ids + nmr, ids + first[k], nr * sizeof(*ids));
+            src[nm] = src[k];
+            slen[nm] = slen[k];
+            want[nm] = want[k];
+            fill[nm] = nr;
+            nm++;
+            nmr += nr;
+        }
+    if (nm) {
+        first[0] = 0;
+        for (size_t k = 0; k < nm; k++)
+            first[k + 1] = first[k] + fill[k];
+        for (size_t j = 0; j < nmr; j++)
+            err[ids[j]] = LZO_E_ERROR;
+        C.concat = 1;
+        rc = pom_col_read_chunked(src, slen, nm, &C);
+    }
+out:
+    free(slot);
+    free(first);
+    free(fill);
+    free(ids);
+    free(src);
+    free(slen);
+    free(want);
+    free(st);
     return rc;
 }

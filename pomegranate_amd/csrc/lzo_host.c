@@ -26,6 +26,7 @@
 #include "lzo_mi355x.h"
 #include "lzo_mi355x_kernels.h"
 #include "minilzo.h"
+#include "pom_column.h"
 #include "pom_gc.h"
 
 /* Debug and experiment switches: ONE environment variable, POM_LZO_DEBUG,
@@ -545,6 +546,9 @@ struct layout {
     /* OP_GC_SCAN chunks (gc_layout_make) */
     size_t nlzo, rcap;
     size_t o_scanoff, o_first, o_live, o_nranges, o_err, o_adepth, o_hrng;
+    /* OP_COL_READ chunks (cr_layout_make) */
+    size_t nreq, res_hdr, res_bytes;
+    size_t o_want, o_outoff, o_req, o_res, o_hres;
 };
 
 static void layout_make(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
@@ -612,7 +616,7 @@ static void layout_fill(const struct layout *L, uint8_t *h, const uint8_t *const
     }
 }
 
-enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN };
+enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ };
 
 /* One host batch: the caller's arrays, the capacities the kernels use, and
  * the plan (device split, largest-first order). */
@@ -636,6 +640,7 @@ struct hbatch {
     pom_chunk_fn pre_chunk; /* called with a chunk's block ids before its inputs are staged */
     void *cb_ctx;
     struct pom_gc_sink *gc; /* OP_GC_SCAN: the walk's per-block inputs and results */
+    struct pom_col_sink *cr; /* OP_COL_READ: the columns' requests and their results */
 };
 
 /* debug key host_timing=1: per-batch and per-chunk wall times on stderr (diagnostic) */
@@ -1118,6 +1123,221 @@ void pom_gc_sink_free(struct pom_gc_sink *sink)
     }
 }
 
+/* ------------------------------------------------------------------------ */
+/* OP_COL_READ chunks: decode, region copy (col_slice.hip), slices back       */
+/* ------------------------------------------------------------------------ */
+/* A column and all its requests are in one chunk; request j of the chunk is
+ * the j-th in block order, then in the block's own order.  The recorded
+ * length, the offset and the size are all known here, so every request's
+ * clamped length and its 16-byte-aligned place among the chunk's slices are
+ * known before the launch: one copy of a known size brings back codes and
+ * slices, with no sizing round trip between two copies (the bytes of a request
+ * that ends in an error are copied and ignored).  That copy is queued once the
+ * chunk's kernels are done, as chunk_collect queues its own.  Queued with the
+ * launch, the chunks' decodes ran one after another instead of side by side
+ * (64 columns of 4 MiB, 32 reads each: 83 ms a call against 36 ms; DESIGN
+ * 5.7) -- as if the copy, waiting for its chunk's decode, held up the next
+ * chunks' copies to the device, and with them their kernels.  Staging (host and
+ * device alike up to the inputs' end):
+ *   [src_off u64][dst_off u64][want u64][out_off u64, nreq][requests, nreq][src_len u32][dst_cap u32]
+ *   [src bytes, 16-B aligned per block]
+ *   device: [decoded columns, 16-B aligned][decoder scratch]
+ *   both:   [status i32][out_len u32][slice len u32, nreq][slice err i32, nreq][slices]  <- D2H, one copy
+ * No other decoded byte leaves the device. */
+static size_t cr_slot(const struct pom_col_sink *C, size_t b, size_t k)
+{
+    const struct pom_col_req *q = &C->req[C->req_ids[k]];
+    const uint64_t w = C->want[b];
+    const uint64_t n = q->offset > w ? 0 : q->size < w - q->offset ? q->size : w - q->offset;
+    return ALIGN_UP((size_t)n, 16);
+}
+
+static void cr_layout_make(struct layout *L, const size_t *ids, size_t nb, const struct hbatch *B)
+{
+    const struct pom_col_sink *C = B->cr;
+    memset(L, 0, sizeof(*L));
+    L->nb = nb;
+    L->ids = ids;
+    size_t s = 0, d = 0, nr = 0, sl = 0;
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = ids[i];
+        s += ALIGN_UP(B->src_len[b], 16);
+        d += ALIGN_UP(B->cap[b], 16);
+        for (size_t k = C->req_first[b]; k < C->req_first[b + 1]; k++, nr++)
+            sl += cr_slot(C, b, k);
+    }
+    L->nreq = nr;
+    size_t o = 0;
+    L->o_srcoff = o; o += 8 * nb;
+    L->o_dstoff = o; o += 8 * nb;
+    L->o_want = o; o += 8 * nb;
+    L->o_outoff = o; o += 8 * nr;
+    L->o_req = o; o += sizeof(struct pom_col_req) * nr;
+    L->o_srclen = o; o += 4 * nb;
+    L->o_dstcap = o; o += 4 * nb;
+    o = ALIGN_UP(o, 256);
+    L->o_src = o;
+    o += ALIGN_UP(s, 256);
+    L->o_dst = o;
+    L->res_hdr = ALIGN_UP(8 * nb + 8 * nr, 16);
+    L->res_bytes = L->res_hdr + sl;
+    L->o_hres = o;
+    L->htotal = o + L->res_bytes;
+    o += ALIGN_UP(d, 256);
+    L->o_scr = o;
+    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nb), 256);
+    L->o_res = o;
+    L->o_status = o;
+    L->o_outlen = o + 4 * nb;
+    L->dtotal = o + L->res_bytes;
+}
+
+static void cr_layout_fill(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    const struct pom_col_sink *C = B->cr;
+    uint64_t *so = (uint64_t *)(h + L->o_srcoff);
+    uint64_t *dof = (uint64_t *)(h + L->o_dstoff);
+    uint64_t *wt = (uint64_t *)(h + L->o_want);
+    uint64_t *oo = (uint64_t *)(h + L->o_outoff);
+    struct pom_col_req *rq = (struct pom_col_req *)(h + L->o_req);
+    uint32_t *sl = (uint32_t *)(h + L->o_srclen);
+    uint32_t *dc = (uint32_t *)(h + L->o_dstcap);
+    size_t s = 0, d = 0, j = 0, at = 0;
+    struct copy_job *jobs = malloc(L->nb * sizeof(*jobs));
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        so[i] = s;
+        dof[i] = d;
+        wt[i] = C->want[b];
+        sl[i] = (uint32_t)B->src_len[b];
+        dc[i] = (uint32_t)B->cap[b];
+        for (size_t k = C->req_first[b]; k < C->req_first[b + 1]; k++, j++) {
+            const struct pom_col_req *q = &C->req[C->req_ids[k]];
+            rq[j].offset = q->offset;
+            rq[j].size = q->size;
+            rq[j].col = (uint32_t)i;            /* the chunk's own column index */
+            rq[j].pad = 0;
+            oo[j] = at;
+            at += cr_slot(C, b, k);
+        }
+        if (jobs) {
+            jobs[i].dst = h + L->o_src + s;
+            jobs[i].src = B->src[b];
+            jobs[i].len = B->src_len[b];
+        } else if (B->src_len[b]) {
+            memcpy(h + L->o_src + s, B->src[b], B->src_len[b]);
+        }
+        s += ALIGN_UP(B->src_len[b], 16);
+        d += ALIGN_UP(B->cap[b], 16);
+    }
+    if (jobs) {
+        copy_jobs(jobs, L->nb);
+        free(jobs);
+    }
+}
+
+/* As chunk_launch: everything queued on the slot's stream, nothing waited for. */
+static int cr_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
+{
+    if (L->nreq > 0xFFFFFFFFu || slot_reserve(S, L->dtotal, L->htotal) != 0)
+        return -1;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    hipStream_t s = S->stream;
+    const uint32_t nb = (uint32_t)L->nb;
+    const double t0 = g_timing ? now_ms() : 0;
+    cr_layout_fill(L, h, B);
+    if (g_timing)
+        fprintf(stderr, "  chunk n=%u, %zu requests: fill %.2f ms (%zu B)\n", nb, L->nreq, now_ms() - t0, L->htotal);
+    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
+        return -1;
+    const uint64_t *so = (const uint64_t *)(d + L->o_srcoff);
+    const uint64_t *dof = (const uint64_t *)(d + L->o_dstoff);
+    const uint32_t *sl = (const uint32_t *)(d + L->o_srclen);
+    const uint32_t *dc = (const uint32_t *)(d + L->o_dstcap);
+    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
+    int32_t *st = (int32_t *)(d + L->o_status);
+    uint32_t *rl = (uint32_t *)(d + L->o_res + 8 * L->nb);
+    int32_t *re = (int32_t *)(d + L->o_res + 8 * L->nb + 4 * L->nreq);
+    const int rc = B->cr->concat
+        ? lzo_mi355x_launch_decompress_concat(d + L->o_src, so, sl, d + L->o_dst, dof, dc, ol, st, nb, s)
+        : decompress_dev(d + L->o_src, so, sl, d + L->o_dst, dof, dc, ol, st, nb, d + L->o_scr, 0, s);
+    if (rc != 0 ||
+        lzo_mi355x_launch_col_slice(d + L->o_dst, dof, ol, st, (const uint64_t *)(d + L->o_want), nb,
+                                    (const struct pom_col_req *)(d + L->o_req), (uint32_t)L->nreq,
+                                    d + L->o_res + L->res_hdr, (const uint64_t *)(d + L->o_outoff), rl, re,
+                                    s) != 0)
+        return -1;
+    return 0;
+}
+
+/* As chunk_collect: once the chunk's kernels are done, the one D2H of codes and slices. */
+static int cr_chunk_collect(struct slot *S, struct layout *L, int poll)
+{
+    if (L->collected)
+        return 1;
+    hipStream_t s = S->stream;
+    if (poll) {
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady)
+            return 0;
+        if (q != hipSuccess)
+            return -1;
+    } else if (hipStreamSynchronize(s) != hipSuccess) {
+        return -1;
+    }
+    if (hipMemcpyAsync(S->hmem + L->o_hres, S->dmem + L->o_res, L->res_bytes, hipMemcpyDeviceToHost, s) !=
+        hipSuccess)
+        return -1;
+    L->packed = L->res_bytes;
+    L->collected = 1;
+    return 1;
+}
+
+/* As chunk_deliver: the next chunk's copy runs while this one is unpacked. */
+static int cr_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
+                            struct slot *nS, struct layout *nL)
+{
+    const double t0 = g_timing ? now_ms() : 0;
+    if (cr_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
+        return -1;
+    if (nS && cr_chunk_collect(nS, nL, 0) < 0)
+        return -1;
+    const double t1 = g_timing ? now_ms() : 0;
+    struct pom_col_sink *C = B->cr;
+    const uint8_t *res = S->hmem + L->o_hres;
+    const uint64_t *oo = (const uint64_t *)(S->hmem + L->o_outoff);
+    const int32_t *hst = (const int32_t *)res;
+    const uint32_t *hrl = (const uint32_t *)(res + 8 * L->nb);
+    const int32_t *hre = (const int32_t *)(res + 8 * L->nb + 4 * L->nreq);
+    struct copy_job *jobs = malloc((L->nreq + 1) * sizeof(*jobs));
+    size_t j = 0;
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        C->status[b] = hst[i];
+        for (size_t k = C->req_first[b]; k < C->req_first[b + 1]; k++, j++) {
+            const size_t r = C->req_ids[k];
+            const size_t n = hre[j] == 0 ? hrl[j] : 0;
+            C->err[r] = hre[j];
+            C->out_len[r] = n;
+            if (jobs) {
+                jobs[j].dst = C->out[r];
+                jobs[j].src = res + L->res_hdr + oo[j];
+                jobs[j].len = n;
+            } else if (n) {
+                memcpy(C->out[r], res + L->res_hdr + oo[j], n);
+            }
+        }
+    }
+    if (jobs) {
+        copy_jobs(jobs, L->nreq);
+        free(jobs);
+    }
+    if (g_timing)
+        fprintf(stderr, "  deliver n=%zu: wait %.2f (%zu B) unpack %.2f ms\n", L->nb, t1 - t0, L->packed,
+                now_ms() - t1);
+    return 0;
+}
+
 /* A host batch is cut into chunks of at most kChunkBudget bytes of input plus
  * output capacity (a larger block is a chunk of its own), pipelined through
  * the device's kSlots slots: chunk k is staged and its copies and kernels are
@@ -1184,6 +1404,7 @@ static int dev_run(void *arg, int d)
         }
         /* walk chunks put their LZO blocks first (gc_partition): in a copy of the ids */
         const int gc = B->kind == OP_GC_SCAN;
+        const int cr = B->kind == OP_COL_READ;
         if (gc && !rev) {
             if ((rev = malloc(nids * sizeof(*rev))) != NULL) {
                 memcpy(rev, ids, nids * sizeof(*rev));
@@ -1225,8 +1446,8 @@ static int dev_run(void *arg, int d)
             if (dj >= 0) {
                 const int ahead = !B->ooo && live[nxt] && nxt != dj;
                 const int fail = fail_at >= 0 && ndeliv++ == fail_at;
-                if (fail || (gc ? gc_chunk_deliver : chunk_deliver)(&c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL,
-                                                                     &L[nxt]) != 0) {
+                if (fail || (gc ? gc_chunk_deliver : cr ? cr_chunk_deliver : chunk_deliver)(
+                                &c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL, &L[nxt]) != 0) {
                     rc = -1;
                     for (int j = 0; j < B->nslots; j++)
                         hipStreamSynchronize(c->s[j].stream);
@@ -1245,6 +1466,8 @@ static int dev_run(void *arg, int d)
                 if (gc)
                     gc_layout_make(&L[cur], ids + from, end - from,
                                    gc_partition(rev + from, end - from, B->gc->is_lzo), B->src_len, B->cap);
+                else if (cr)
+                    cr_layout_make(&L[cur], ids + from, end - from, B);
                 else
                     layout_make(&L[cur], ids + from, end - from, B->src_len, B->cap,
                                 B->kind == OP_COMPRESS);
@@ -1252,7 +1475,7 @@ static int dev_run(void *arg, int d)
                  * while the chunks in flight are copied and decoded */
                 if (B->pre_chunk)
                     B->pre_chunk(B->cb_ctx, ids + from, end - from);
-                if ((gc ? gc_chunk_launch : chunk_launch)(&c->s[cur], &L[cur], B) != 0) {
+                if ((gc ? gc_chunk_launch : cr ? cr_chunk_launch : chunk_launch)(&c->s[cur], &L[cur], B) != 0) {
                     rc = -1;
                     hipStreamSynchronize(c->s[cur].stream);
                 } else {
@@ -1312,12 +1535,12 @@ static int batch_devices(int *devs)
 static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                            uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
                            pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
-                           struct pom_gc_sink *gc);
+                           struct pom_gc_sink *gc, struct pom_col_sink *cr);
 
 static int batch_common(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                         uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks)
 {
-    return batch_common_cb(kind, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL, NULL);
+    return batch_common_cb(kind, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* lzo_mi355x_decompress_batch with pre_chunk(ctx, ids, nb) called before each
@@ -1328,7 +1551,7 @@ int pom_decompress_batch_chunked(const uint8_t *const *src, const size_t *src_le
                                  size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn pre_chunk,
                                  void *ctx)
 {
-    return batch_common_cb(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx, NULL);
+    return batch_common_cb(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx, NULL, NULL);
 }
 
 /* lzo_mi355x_compress_batch with on_chunk(ctx, ids, nb) called as each chunk's
@@ -1339,13 +1562,13 @@ int pom_compress_batch_chunked(const uint8_t *const *src, const size_t *src_len,
                                size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn on_chunk,
                                void *ctx)
 {
-    return batch_common_cb(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx, NULL);
+    return batch_common_cb(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx, NULL, NULL);
 }
 
 static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                            uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
                            pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
-                           struct pom_gc_sink *gc)
+                           struct pom_gc_sink *gc, struct pom_col_sink *cr)
 {
     const double t0 = g_timing ? now_ms() : 0;
     struct tctx *t = tctx_get();
@@ -1372,14 +1595,18 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
             free(cost);
             return LZO_E_ERROR;
         }
-        cap[b] = kind == OP_COMPRESS ? lzo_mi355x_worst_compress(src_len[b]) : gc ? gc->cap[b] : dst_len[b];
+        cap[b] = kind == OP_COMPRESS ? lzo_mi355x_worst_compress(src_len[b]) : gc ? gc->cap[b]
+                 : cr ? (size_t)cr->want[b] : dst_len[b];
         if (cap[b] > 0xFFFFFFF0u)
             cap[b] = 0xFFFFFFF0u;
         cost[b] = src_len[b] + cap[b];
+        if (cr)                                 /* the chunk budget counts the slices too */
+            for (size_t k = cr->req_first[b]; k < cr->req_first[b + 1]; k++)
+                cost[b] += cr_slot(cr, b, k);
     }
     struct hbatch B = {kind, src, src_len, dst, dst_len, status, cap, cost,
                        kind == OP_COMPRESS ? kChunkBudgetCompress : kChunkBudget,
-                       {0, 1, NULL, NULL}, devs, t, 0, kSlots, 0, on_chunk, pre_chunk, cb_ctx, gc};
+                       {0, 1, NULL, NULL}, devs, t, 0, kSlots, 0, on_chunk, pre_chunk, cb_ctx, gc, cr};
     B.ooo = kind == OP_COMPRESS && pom_dbg_int("ooo", 1) != 0;
     /* compress chunks that fit the LDS encoder's 4 blocks per CU at once use
      * it: a block alone on its CU finishes twice as fast as with the
@@ -1398,13 +1625,13 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
             status[b] = LZO_E_ERROR;
             if (gc)
                 gc->err[b] = LZO_E_ERROR;
-            else
+            else if (!cr)                       /* (a column read's requests: set by the caller) */
                 dst_len[b] = 0;
         }
         rc = pom_run_devices(B.plan.ndev, dev_run, &B) == 0 ? LZO_E_OK : LZO_E_ERROR;
         if (g_timing)
             fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n",
-                    kind == OP_COMPRESS ? "compress" : gc ? "gc scan" : "decompress", nblocks, B.plan.ndev,
+                    kind == OP_COMPRESS ? "compress" : gc ? "gc scan" : cr ? "column read" : "decompress", nblocks, B.plan.ndev,
                     now_ms() - t0);
         pom_plan_free(&B.plan);
     }
@@ -1420,7 +1647,14 @@ int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t
         sink->out_len[b] = sink->live[b] = sink->nranges[b] = 0;
         sink->rng[b] = NULL;
     }
-    return batch_common_cb(OP_GC_SCAN, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink);
+    return batch_common_cb(OP_GC_SCAN, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL);
+}
+
+int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                         struct pom_col_sink *sink)
+{
+    return batch_common_cb(OP_COL_READ, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, NULL,
+                           sink);
 }
 
 int lzo_mi355x_compress_batch(const uint8_t *const *src, const size_t *src_len,

@@ -190,6 +190,36 @@ int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t
                         struct pom_gc_sink *sink);
 void pom_gc_sink_free(struct pom_gc_sink *sink);
 
+/* Column reads by offset and size (col_slice.hip): pom_col_slice_dev of
+ * include/pom_column.h, one launch on `stream`. */
+struct pom_col_req;
+int lzo_mi355x_launch_col_slice(const uint8_t *data, const uint64_t *data_off,
+                                const uint32_t *data_len, const int32_t *status,
+                                const uint64_t *want, uint32_t ncol, const struct pom_col_req *req,
+                                uint32_t nreq, uint8_t *out, const uint64_t *out_off,
+                                uint32_t *out_len, int32_t *err, hipStream_t stream);
+
+/* Host side (lzo_host.c), not part of the ABI: the chunk pipeline of the host
+ * batches with the region copy queued behind each chunk's decode
+ * (column_codec.c).  Block b is an LZO1X stream of src_len[b] bytes at src[b],
+ * decoded on the GPU with capacity want[b] (concat: as consecutive streams);
+ * its requests are req[req_ids[k]] for k in [req_first[b], req_first[b + 1])
+ * (their col is not read: the block is the column).  Per block the decoder's
+ * status; per request out_len and err as pom_col_slice_dev, and the bytes in
+ * out[].  Only the slices are copied back. */
+struct pom_col_sink {
+    const uint64_t *want;
+    const size_t *req_first, *req_ids;
+    const struct pom_col_req *req;
+    uint8_t *const *out;
+    size_t *out_len;
+    int *err;
+    int32_t *status;
+    int concat;
+};
+int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                         struct pom_col_sink *sink);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,7 @@ EXPORTS = (
     "pom_itb_read_batch", "pom_itb_read_lzo_decompress_batch",
     # include/pom_column.h
     "pom_col_zip_bound", "pom_col_zip_batch", "pom_col_zipv", "pom_col_unzip_batch",
+    "pom_col_read_batch", "pom_col_slice_dev",
     # include/pom_xnet.h
     "pom_xnet_frame", "pom_xnet_parse", "pom_xnet_itb_reply_batch", "pom_xnet_itb_wb_batch",
     "pom_xnet_itb_recv_batch",

@@ -1,0 +1,281 @@
+"""GPU: column reads by offset and size (include/pom_column.h) --
+pom_col_slice_dev in one launch on guarded arenas against Python slices, and
+pom_col_read_batch through the host chunk pipeline against column.zip_batch
+output sliced in Python, the error rules, the reference's hvfs_fwritev
+fixtures and a multi-chunk run."""
+from __future__ import annotations
+
+import random
+import struct
+
+import numpy as np
+import pytest
+
+from gpu_util import assert_guards, guarded_batch
+from pomegranate_amd import column, lzo, synth
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+EINVAL = -22
+U64 = 2 ** 64 - 1
+FILL = 0xA5
+TILE = 4096
+LENGTHS = [0, 1, 15, 16, 17, 31, 33, TILE - 1, TILE, TILE + 1]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    d = torch.device("cuda:0")
+    torch.cuda.set_device(d)
+    return d
+
+
+@pytest.fixture(autouse=True)
+def _needs_gpu(dev):
+    """The host batches pick the device themselves; without one they skip too."""
+
+
+@pytest.fixture
+def debug_env(monkeypatch):
+    def set_(value):
+        monkeypatch.setenv("POM_LZO_DEBUG", value)      # (lzo_host.c pom_dbg_str)
+        lzo.debug_reload()
+    yield set_
+    monkeypatch.delenv("POM_LZO_DEBUG", raising=False)
+    lzo.debug_reload()
+
+
+def expect(cols, status, want, req):
+    """(err, bytes) of one request by the rules of pom_column.h."""
+    c, offset, size = req
+    if c >= len(cols):
+        return EINVAL, b""
+    if status[c] != 0:
+        return status[c], b""
+    if len(cols[c]) != want[c]:
+        return lzo.LZO_E_ERROR, b""
+    if offset > want[c]:
+        return EINVAL, b""
+    return 0, cols[c][offset: min(offset + size, want[c])]
+
+
+# ---------------------------------------------------------------------------
+# pom_col_slice_dev: one launch on guarded arenas
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def dev_run(dev):
+    """One launch.  Columns 0 ... 15 stand at the residues 0 ... 15 mod 16 and
+    hold the sweep (source offsets 0-17, destination alignments 0-15, the
+    lengths around a granule and a tile, twice over different columns: more
+    requests than the capped grid has rows).  Column 16 takes a request of two
+    tiles + 1 at a misaligned offset and many requests more; column 17 has a
+    decoder code, column 18 another length than recorded."""
+    rng = np.random.default_rng(0xC01)
+    cols = [rng.integers(0, 256, 17 + TILE + 1 + (i % 4), dtype=np.uint8).tobytes() for i in range(16)]
+    cols += [rng.integers(0, 256, 3 * TILE + 77, dtype=np.uint8).tobytes(),
+             rng.integers(0, 256, 500, dtype=np.uint8).tobytes(), rng.integers(0, 256, 500, dtype=np.uint8).tobytes()]
+    shifts = list(range(16)) + [5, 3, 9]
+    status = [0] * 19
+    status[17] = lzo.LZO_E_LOOKBEHIND_OVERRUN
+    want = [len(c) for c in cols]
+    want[18] += 1
+    reqs, align = [], []
+    for rep in range(2):
+        for offset in range(18):
+            for a in range(16):
+                for n in LENGTHS:
+                    reqs.append(((offset + a + 7 * rep) % 16, offset, n))
+                    align.append(a)
+    W = want[16]
+    many = [(16, 13, 2 * TILE + 1), (16, 0, W), (16, 0, U64), (16, W - 1, U64), (16, W, 10), (16, W, 0),
+            (16, W + 1, 10), (16, U64, U64), (16, W - 100, 200), (16, 1, W), (16, 7, 0)]
+    many += [(16, int(o), int(n)) for o, n in zip(rng.integers(0, W, 30), rng.integers(0, 3 * TILE, 30))]
+    many += [(17, 0, 100), (17, 499, 1), (18, 0, 100), (18, 500, 1), (18, 501, 0), (19, 0, 1), (2 ** 32 - 1, 0, 1)]
+    for i, q in enumerate(many):
+        reqs.append(q)
+        align.append((3 * i + 1) % 16)
+    exp = [expect(cols, status, want, q) for q in reqs]
+    # room: the bytes a request may write; 64 where it must write nothing
+    room = [len(b) if e == 0 else 64 for e, b in exp]
+    src = guarded_batch(torch, cols, dev, shifts, fill=0xEE)
+    dst = guarded_batch(torch, room, dev, align, fill=FILL)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    req = np.array([(o, s, c) for c, o, s in reqs], dtype=np.uint64)
+    nreq = len(reqs)
+    out_len = torch.full((nreq,), 99, dtype=torch.int32, device=dev)
+    err = torch.full((nreq,), 99, dtype=torch.int32, device=dev)
+    column.slice_dev(src, t(np.array(want, dtype=np.int64)), t(req.view(np.int64)), dst.arena, dst.off, out_len,
+                     err, status=t(np.array(status, dtype=np.int32)))
+    torch.cuda.synchronize()
+    return {"reqs": reqs, "align": align, "exp": exp, "dst": dst, "src": src, "cols": cols,
+            "out_len": out_len.cpu().numpy().view(np.uint32), "err": err.cpu().numpy()}
+
+
+def test_dev_codes_and_lengths(dev_run):
+    R = dev_run
+    assert len(R["reqs"]) > 4096
+    for r, (e, b) in enumerate(R["exp"]):
+        assert (int(R["err"][r]), int(R["out_len"][r])) == (e, len(b)), (r, R["reqs"][r])
+    errs = {e for e, _ in R["exp"]}
+    assert errs == {0, EINVAL, lzo.LZO_E_ERROR, lzo.LZO_E_LOOKBEHIND_OVERRUN}
+
+
+def test_dev_bytes_and_guards(dev_run):
+    """Every slice equals the Python slice; nothing is written outside
+    [out_off[r], out_off[r] + out_len[r]) -- for the requests that end in an
+    error, nothing at all -- and the columns' arena is as it was."""
+    R = dev_run
+    arena = assert_guards(R["dst"], [len(b) for _, b in R["exp"]], FILL)
+    off = R["dst"].host_off
+    bad = [(r, R["reqs"][r], R["align"][r]) for r, (_, b) in enumerate(R["exp"])
+           if arena[int(off[r]): int(off[r]) + len(b)].tobytes() != b]
+    assert not bad, (len(bad), bad[:8])
+    src = R["src"].arena.cpu().numpy()
+    for c, o in zip(R["cols"], R["src"].host_off.tolist()):
+        assert src[o: o + len(c)].tobytes() == c
+
+
+def test_dev_sweep_is_complete(dev_run):
+    """The sweep holds every (source offset, destination alignment, length)."""
+    seen = {(o, a, n) for (c, o, n), a in zip(dev_run["reqs"], dev_run["align"]) if c < 16}
+    assert seen == {(o, a, n) for o in range(18) for a in range(16) for n in LENGTHS}
+    assert (16, 13, 2 * TILE + 1) in dev_run["reqs"]
+
+
+def test_dev_no_requests(dev):
+    """nreq = 0 launches nothing."""
+    src = guarded_batch(torch, [b"abc"], dev, [0], fill=0xEE)
+    z = torch.zeros(0, dtype=torch.int64, device=dev)
+    out = torch.full((64,), FILL, dtype=torch.uint8, device=dev)
+    column.slice_dev(src, torch.tensor([3], dtype=torch.int64, device=dev), z.view(0, 3), out, z,
+                     torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev))
+    torch.cuda.synchronize()
+    assert (out.cpu().numpy() == FILL).all()
+
+
+# ---------------------------------------------------------------------------
+# pom_col_read_batch through the host pipeline
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def zipped(dev):
+    """Seven compressible columns and their zipped form (column.zip_batch)."""
+    cols = [synth.block(synth.ITB, 900 + i, n) for i, n in enumerate([100000, 5000, 70001, 4096, 3333])]
+    cols += [synth.block(synth.TEXT, 910, 20000), synth.block(synth.ZEROS, 911, 300000)]
+    cols = [bytes(c) for c in cols]
+    zips, comp = column.zip_batch(cols)
+    assert comp == [1] * len(cols)
+    return cols, zips
+
+
+def read_and_check(cols, zips, reqs, want_err=None):
+    """reqs (col, offset, size) against the Python slices of cols; want_err
+    {r: code} for the requests that must fail."""
+    want_err = want_err or {}
+    room = [0 if r in want_err else max(min(s, len(cols[c])), 1) for r, (c, o, s) in enumerate(reqs)]
+    outs, err = column.read_batch(zips, reqs, room=room)
+    for r, (c, o, s) in enumerate(reqs):
+        if r in want_err:
+            assert (err[r], outs[r]) == (want_err[r], b""), (r, reqs[r])
+        else:
+            assert err[r] == 0 and outs[r] == cols[c][o: o + s], (r, reqs[r], err[r], len(outs[r]))
+    return outs, err
+
+
+def test_read_round_trip(zipped):
+    cols, zips = zipped
+    rnd = random.Random(5)
+    reqs = [(c, 0, len(cols[c])) for c in range(len(cols))]
+    reqs += [(c, 0, U64) for c in range(len(cols))]
+    for c in range(len(cols)):
+        n = len(cols[c])
+        reqs += [(c, n, 5), (c, n - 1, 5), (c, 1, n), (c, n // 2, 0), (c, 17, 4096), (c, n // 3, 33)]
+        reqs += [(c, rnd.randrange(n), rnd.randrange(2 * n)) for _ in range(6)]
+    rnd.shuffle(reqs)
+    read_and_check(cols, zips, reqs)
+
+
+def test_read_one_request_and_none(zipped):
+    cols, zips = zipped
+    read_and_check(cols, zips, [(2, 12345, 4096)])
+    assert column.read_batch(zips, []) == ([], [])
+
+
+def test_read_error_rules(zipped, oracle):
+    """Every rule of pom_column.h, in one call with good reads between."""
+    cols, zips = zipped
+    W = len(cols[1])
+    cut = zips[1][:-9]                                           # a truncated stream
+    cut_rc, _ = oracle.decompress_safe(cut[8:], W)
+    assert cut_rc != 0
+    longer = struct.pack("<Q", W + 1) + zips[1][8:]              # wrong header lengths
+    shorter = struct.pack("<Q", W - 1) + zips[1][8:]
+    over_rc, _ = oracle.decompress_safe(zips[1][8:], W - 1)
+    assert over_rc == lzo.LZO_E_OUTPUT_OVERRUN
+    impossible = struct.pack("<Q", 255 * (len(zips[1]) - 8) + 1) + zips[1][8:]
+    beyond_abi = struct.pack("<Q", 0xFFFFFFF1) + zips[1][8:]
+    huge = struct.pack("<Q", U64) + zips[1][8:]
+    stored = [zips[0], cut, longer, shorter, b"1234567", b"", impossible, beyond_abi, huge, zips[1], zips[4]]
+    plain = [cols[0], b"", b"", b"", b"", b"", b"", b"", b"", cols[1], cols[4]]
+    reqs = [(0, 10, 100), (1, 0, 10), (2, 0, 10), (3, 0, 10), (4, 0, 10), (5, 0, 0), (6, 0, 10), (7, 0, 10),
+            (8, 0, 10), (9, W, 10), (9, W + 1, 10), (9, U64, U64), (11, 0, 10), (2 ** 32 - 1, 0, 10),
+            (10, 300, 100), (9, 0, W), (1, W + 5, 1)]
+    want_err = {1: cut_rc, 2: lzo.LZO_E_ERROR, 3: over_rc, 4: lzo.LZO_E_ERROR, 5: lzo.LZO_E_ERROR,
+                6: lzo.LZO_E_ERROR, 7: lzo.LZO_E_ERROR, 8: lzo.LZO_E_ERROR, 10: EINVAL, 11: EINVAL, 12: EINVAL,
+                13: EINVAL, 16: cut_rc}
+    outs, err = read_and_check(plain, stored, reqs, want_err)
+    assert (err[9], outs[9]) == (0, b"")                         # offset == W: a valid empty read
+
+
+def test_read_reference_fwritev_columns(fwritev_columns):
+    """The reference writer's layout (one stream per iovec), sliced across the
+    stream boundaries, mixed with a single-stream column."""
+    fx = fwritev_columns
+    cols, zips = list(fx["data"]), list(fx["zips"])
+    extra, comp = column.zip_batch([fx["data"][2]])
+    assert comp == [1]
+    cols.append(fx["data"][2])
+    zips.append(extra[0])
+    reqs = []
+    for c, iov in enumerate(fx["iov_len"]):
+        at = 0
+        for n in iov[:-1]:
+            at += n
+            reqs += [(c, max(at - 3, 0), 7), (c, at, 1), (c, max(at - 1, 0), U64)]
+        reqs += [(c, 0, len(cols[c])), (c, len(cols[c]), 1)]
+    reqs += [(len(cols) - 1, 5, 50), (len(cols) - 1, 0, U64)]
+    assert any(len(iov) > 1 for iov in fx["iov_len"])
+    read_and_check(cols, zips, reqs)
+    # damaged multi-stream columns fail like a damaged single stream
+    i = fx["names"].index("fuse_pages")
+    z, d = fx["zips"][i], fx["data"][i]
+    bad_len = struct.pack("<Q", len(d) + 1) + z[8:]
+    short = struct.pack("<Q", len(d) - 1) + z[8:]
+    outs, err = column.read_batch([z[:-2], bad_len, short, z], [(0, 0, 4), (1, 0, 4), (2, 0, 4), (3, 1, 4)])
+    assert err[0] != 0 and err[1] == lzo.LZO_E_ERROR and err[2] == lzo.LZO_E_OUTPUT_OVERRUN
+    assert outs[:3] == [b""] * 3 and (err[3], outs[3]) == (0, d[1:5])
+
+
+def test_read_unreferenced_damaged_column(zipped):
+    """A column no request names takes no part: damaged, it disturbs nothing,
+    and even one that could not be staged is never looked at."""
+    cols, zips = zipped
+    stored = [zips[0], zips[1][:20], struct.pack("<Q", U64), zips[3], b""]
+    read_and_check([cols[0], b"", b"", cols[3], b""], stored, [(3, 5, 100), (0, 99000, 5000), (3, 0, U64)])
+
+
+def test_read_spans_chunks(dev, debug_env):
+    """chunk_mb=1: 40 columns of 100 KiB take several chunks; three shuffled
+    requests each, so a chunk delivers requests from all over the caller's
+    arrays."""
+    cols = [bytes(synth.block(synth.ITB, 1000 + i, 100 * 1024)) for i in range(40)]
+    zips, comp = column.zip_batch(cols)
+    assert comp == [1] * 40
+    rnd = random.Random(40)
+    reqs = [(c, rnd.randrange(100 * 1024), rnd.randrange(1, 64 * 1024)) for c in range(40) for _ in range(3)]
+    rnd.shuffle(reqs)
+    debug_env("chunk_mb=1")
+    read_and_check(cols, zips, reqs)
