@@ -30,6 +30,28 @@ static uint16_t rd16(const uint8_t *p)
     return v;
 }
 
+int pom_itb_walk_header(const uint8_t *rec, size_t rec_len, struct pom_walk_block *w)
+{
+    if (rec_len < POM_ITBH_SIZE)
+        return -EINVAL;
+    const uint32_t len = rd32(rec + POM_ITBH_LEN_OFF), zlen = rd32(rec + POM_ITBH_ZLEN_OFF);
+    const uint16_t algo = rd16(rec + POM_ITBH_ALGO_OFF);
+    const uint8_t ad = rec[POM_ITBH_ADEPTH_OFF];
+    if (len < POM_ITBH_SIZE || len > rec_len || (algo != POM_COMPR_NONE && algo != POM_COMPR_LZO) ||
+        ad == 0 || ad > POM_ITB_ADEPTH_MAX)
+        return -EINVAL;
+    if (algo == POM_COMPR_LZO &&
+        (zlen <= POM_ITBH_SIZE || zlen - POM_ITBH_SIZE > POM_ITB_PAYLOAD_MAX))
+        return -EINVAL;
+    w->src = rec + POM_ITBH_SIZE;
+    w->src_len = len - POM_ITBH_SIZE;
+    w->is_lzo = algo == POM_COMPR_LZO;
+    w->cap = w->is_lzo ? zlen - POM_ITBH_SIZE : 0;
+    w->adepth = ad;
+    w->entries = (int32_t)rd32(rec + POM_ITBH_ENTRIES_OFF);
+    return 0;
+}
+
 int pom_gc_scan_dev(const uint8_t *payload, const uint64_t *payload_off,
                     const uint32_t *payload_len, const int32_t *status,
                     const uint8_t *adepth, uint32_t nitb, int column,
@@ -76,23 +98,15 @@ int pom_gc_scan_batch(const uint8_t *const *rec, const size_t *rec_len, size_t n
             len_ok[b] = 0;
         if (entries_ok)
             entries_ok[b] = 0;
-        if (rec_len[b] < POM_ITBH_SIZE)
-            continue;
-        const uint32_t len = rd32(rec[b] + POM_ITBH_LEN_OFF), zlen = rd32(rec[b] + POM_ITBH_ZLEN_OFF);
-        const uint16_t algo = rd16(rec[b] + POM_ITBH_ALGO_OFF);
-        const uint8_t ad = rec[b][POM_ITBH_ADEPTH_OFF];
-        if (len < POM_ITBH_SIZE || len > rec_len[b] || (algo != POM_COMPR_NONE && algo != POM_COMPR_LZO) ||
-            ad == 0 || ad > POM_ITB_ADEPTH_MAX)
-            continue;
-        if (algo == POM_COMPR_LZO &&
-            (zlen <= POM_ITBH_SIZE || zlen - POM_ITBH_SIZE > POM_ITB_PAYLOAD_MAX))
+        struct pom_walk_block w;
+        if (pom_itb_walk_header(rec[b], rec_len[b], &w) != 0)
             continue;
         idx[m] = b;
-        src[m] = rec[b] + POM_ITBH_SIZE;
-        slen[m] = len - POM_ITBH_SIZE;
-        is_lzo[m] = algo == POM_COMPR_LZO;
-        cap[m] = is_lzo[m] ? zlen - POM_ITBH_SIZE : 0;
-        adepth[m] = ad;
+        src[m] = w.src;
+        slen[m] = w.src_len;
+        is_lzo[m] = w.is_lzo;
+        cap[m] = w.cap;
+        adepth[m] = w.adepth;
         m++;
     }
     G.is_lzo = is_lzo;

@@ -4,13 +4,14 @@
 // load their ITE's column, and a ballot with mbcnt compacts them in bit order.
 // Three stream-ordered launches, no host round trip between them:
 //   itb_scan_count_kernel   live[b], nranges[b], err[b]
-//   itb_scan_prefix_kernel  first[0 .. nitb] = exclusive prefix of nranges (u64)
+//   itb_prefix_kernel       first[0 .. nitb] = exclusive prefix of nranges (u64; itb_prefix.h)
 //   itb_scan_emit_kernel    ranges[first[b] + k], one 16-byte store each
 // The emit kernel reads each live ITE's 16 bytes a second time; beside the
 // decode that fills the payloads this is noise.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "itb_prefix.h"
 #include "itb_scan.h"
 #include "lzo1x_wave.h"
 #include "lzo_mi355x_kernels.h"
@@ -21,13 +22,8 @@ constexpr uint32_t kWave = 64;
 constexpr uint32_t kScanThreads = 256;              // 4 waves: 4 ITBs per workgroup
 constexpr uint32_t kScanWaves = kScanThreads / kWave;
 constexpr uint32_t kScanGridMax = 2048;             // then a grid stride
-constexpr uint32_t kPrefixThreads = 1024;
-
-// Lanes below this one whose bit is set in m.
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
+// a prefix tile's sum fits u32: at most 1024 ranges an ITB
+static_assert((uint64_t)kPrefixThreads << POM_ITB_ADEPTH_MAX <= 0xFFFFFFFFull, "prefix tile");
 
 __global__ __launch_bounds__(kScanThreads) void itb_scan_count_kernel(
     const uint8_t* __restrict__ payload, const uint64_t* __restrict__ payload_off,
@@ -59,36 +55,6 @@ __global__ __launch_bounds__(kScanThreads) void itb_scan_count_kernel(
             err[b] = e;
         }
     }
-}
-
-// One workgroup over tiles of kPrefixThreads counts, the running total carried
-// from tile to tile.
-__global__ __launch_bounds__(kPrefixThreads) void itb_scan_prefix_kernel(
-    const uint32_t* __restrict__ nranges, uint32_t nitb, uint64_t* __restrict__ first)
-{
-    __shared__ uint32_t wsum[kPrefixThreads / kWave];
-    const uint32_t t = threadIdx.x, lane = lane_id(), w = t / kWave;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nitb; base += kPrefixThreads) {
-        const uint32_t i = base + t;
-        const uint32_t v = i < nitb ? nranges[i] : 0u;      // at most 1024 each: a tile's sum fits u32
-        const uint32_t incl = wave_incl_scan(v);
-        if (lane == kWave - 1)
-            wsum[w] = incl;
-        __syncthreads();
-        uint32_t before = 0, tile = 0;
-        for (uint32_t k = 0; k < kPrefixThreads / kWave; k++) {
-            const uint32_t s = wsum[k];
-            before += k < w ? s : 0u;
-            tile += s;
-        }
-        if (i < nitb)
-            first[i] = carry + before + (incl - v);
-        carry += tile;
-        __syncthreads();
-    }
-    if (t == 0)
-        first[nitb] = carry;
 }
 
 __global__ __launch_bounds__(kScanThreads) void itb_scan_emit_kernel(
@@ -150,7 +116,7 @@ extern "C" int lzo_mi355x_launch_gc_scan(const uint8_t* payload, const uint64_t*
     if (nitb)
         hipLaunchKernelGGL(itb_scan_count_kernel, dim3(grid), dim3(kScanThreads), 0, stream, payload,
                            payload_off, payload_len, status, adepth, nitb, column, live, nranges, err);
-    hipLaunchKernelGGL(itb_scan_prefix_kernel, dim3(1), dim3(kPrefixThreads), 0, stream, nranges, nitb, first);
+    hipLaunchKernelGGL(itb_prefix_kernel, dim3(1), dim3(kPrefixThreads), 0, stream, nranges, nitb, first);
     if (nitb && ranges_cap)
         hipLaunchKernelGGL(itb_scan_emit_kernel, dim3(grid), dim3(kScanThreads), 0, stream, payload,
                            payload_off, adepth, nitb, column, nranges, err, first, ranges, ranges_cap);

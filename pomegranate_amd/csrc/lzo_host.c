@@ -28,6 +28,7 @@
 #include "minilzo.h"
 #include "pom_column.h"
 #include "pom_gc.h"
+#include "pom_readdir.h"
 
 /* Debug and experiment switches: ONE environment variable, POM_LZO_DEBUG,
  * a comma-separated list of key=value.  No product path
@@ -546,6 +547,7 @@ struct layout {
     /* OP_GC_SCAN chunks (gc_layout_make) */
     size_t nlzo, rcap;
     size_t o_scanoff, o_first, o_live, o_nranges, o_err, o_adepth, o_hrng;
+    size_t o_bytes;         /* OP_READDIR chunks (rd_layout_make), which share the fields above */
     /* OP_COL_READ chunks (cr_layout_make) */
     size_t nreq, res_hdr, res_bytes;
     size_t o_want, o_outoff, o_req, o_res, o_hres;
@@ -616,7 +618,7 @@ static void layout_fill(const struct layout *L, uint8_t *h, const uint8_t *const
     }
 }
 
-enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ };
+enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ, OP_READDIR };
 
 /* One host batch: the caller's arrays, the capacities the kernels use, and
  * the plan (device split, largest-first order). */
@@ -639,7 +641,7 @@ struct hbatch {
     pom_chunk_fn on_chunk;  /* called with each delivered chunk's block ids, or NULL */
     pom_chunk_fn pre_chunk; /* called with a chunk's block ids before its inputs are staged */
     void *cb_ctx;
-    struct pom_gc_sink *gc; /* OP_GC_SCAN: the walk's per-block inputs and results */
+    struct pom_gc_sink *gc; /* OP_GC_SCAN, OP_READDIR: the walk's per-block inputs and results */
     struct pom_col_sink *cr; /* OP_COL_READ: the columns' requests and their results */
 };
 
@@ -1124,6 +1126,168 @@ void pom_gc_sink_free(struct pom_gc_sink *sink)
 }
 
 /* ------------------------------------------------------------------------ */
+/* OP_READDIR chunks: decode, dentry walk (itb_dents.hip), counts and records */
+/* ------------------------------------------------------------------------ */
+/* OP_GC_SCAN's chunks with the dentry walk in the range walk's place: the same
+ * partition (LZO records first) and the same fill (gc_layout_fill); dnum takes
+ * nranges' place, a bytes word per block is added, and the packed output is
+ * bytes.  Staging:
+ *   [src_off u64][dst_off u64][scan_off u64][first u64, nb + 1][src_len u32][dst_cap u32]
+ *   [status i32][out_len u32][live u32][dnum u32][bytes u32][err i32]   <- D2H, one copy
+ *   [adepth u8]
+ *   [src bytes, 16-B aligned per block]
+ *   host:   [the chunk's records]                                <- D2H, sized after the first
+ *   device: [decoded payloads][decoder scratch][records, 272 bytes for every ITE the payloads can hold]
+ * No other decoded byte leaves the device. */
+static void rd_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo,
+                           const size_t *src_len, const size_t *cap)
+{
+    memset(L, 0, sizeof(*L));
+    L->nb = nb;
+    L->ids = ids;
+    L->nlzo = nlzo;
+    size_t o = 0;
+    L->o_srcoff = o; o += 8 * nb;
+    L->o_dstoff = o; o += 8 * nb;
+    L->o_scanoff = o; o += 8 * nb;
+    L->o_first = o; o += 8 * (nb + 1);
+    L->o_srclen = o; o += 4 * nb;
+    L->o_dstcap = o; o += 4 * nb;
+    L->o_status = o; o += 4 * nb;
+    L->o_outlen = o; o += 4 * nb;
+    L->o_live = o; o += 4 * nb;
+    L->o_nranges = o; o += 4 * nb;
+    L->o_bytes = o; o += 4 * nb;
+    L->o_err = o; o += 4 * nb;
+    L->o_adepth = o; o += nb;
+    o = ALIGN_UP(o, 256);
+    L->o_src = o;
+    size_t s = 0, d = 0, r = 0;
+    for (size_t i = 0; i < nb; i++) {
+        s += ALIGN_UP(src_len[ids[i]], 16);
+        if (i < nlzo)
+            d += ALIGN_UP(cap[ids[i]], 16);
+        r += gc_max_ranges(i < nlzo ? cap[ids[i]] : src_len[ids[i]]) * (POM_DENT_HDR + POM_ITE_NAME_MAX);
+    }
+    L->rcap = r;
+    o += ALIGN_UP(s, 256);
+    L->o_dst = o;
+    L->o_hrng = o;
+    L->htotal = o + r;
+    o += ALIGN_UP(d, 256);
+    L->o_scr = o;
+    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
+    L->o_pack = o;
+    L->dtotal = o + r;
+}
+
+/* As gc_chunk_launch. */
+static int rd_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
+{
+    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
+        return -1;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    hipStream_t s = S->stream;
+    const uint32_t nb = (uint32_t)L->nb;
+    gc_layout_fill(L, h, B);
+    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
+        return -1;
+    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
+    int32_t *st = (int32_t *)(d + L->o_status);
+    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
+                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
+                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
+        lzo_mi355x_launch_readdir(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth, nb,
+                                  (uint32_t *)(d + L->o_live), (uint32_t *)(d + L->o_nranges),
+                                  (uint32_t *)(d + L->o_bytes), (uint64_t *)(d + L->o_first),
+                                  d + L->o_pack, L->rcap, (int32_t *)(d + L->o_err), s) != 0)
+        return -1;
+    return hipMemcpyAsync(h + L->o_status, d + L->o_status, 24 * L->nb, hipMemcpyDeviceToHost, s) ==
+                   hipSuccess ? 0 : -1;
+}
+
+/* As gc_chunk_collect: once the counts are back, the D2H of exactly the chunk's records. */
+static int rd_chunk_collect(struct slot *S, struct layout *L, int poll)
+{
+    if (L->collected)
+        return 1;
+    hipStream_t s = S->stream;
+    if (poll) {
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady)
+            return 0;
+        if (q != hipSuccess)
+            return -1;
+    } else if (hipStreamSynchronize(s) != hipSuccess) {
+        return -1;
+    }
+    const uint32_t *hby = (const uint32_t *)(S->hmem + L->o_bytes);
+    size_t total = 0;
+    for (size_t i = 0; i < L->nb; i++)
+        total += hby[i];
+    if (total > L->rcap)
+        return -1;
+    if (total && hipMemcpyAsync(S->hmem + L->o_hrng, S->dmem + L->o_pack, total, hipMemcpyDeviceToHost, s) !=
+                     hipSuccess)
+        return -1;
+    L->packed = total;
+    L->collected = 1;
+    return 1;
+}
+
+/* As gc_chunk_deliver: the chunk's records into a buffer of their own. */
+static int rd_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
+                            struct slot *nS, struct layout *nL)
+{
+    if (rd_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
+        return -1;
+    if (nS && rd_chunk_collect(nS, nL, 0) < 0)
+        return -1;
+    struct pom_gc_sink *G = B->gc;
+    const uint8_t *h = S->hmem;
+    const int32_t *hst = (const int32_t *)(h + L->o_status);
+    const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
+    const uint32_t *hlv = (const uint32_t *)(h + L->o_live);
+    const uint32_t *hdn = (const uint32_t *)(h + L->o_nranges);
+    const uint32_t *hby = (const uint32_t *)(h + L->o_bytes);
+    const int32_t *her = (const int32_t *)(h + L->o_err);
+    struct pom_gc_buf *buf = malloc(sizeof(*buf) + L->packed);
+    if (!buf)
+        return -1;
+    /* a listing is megabytes where the ranges were kilobytes: block by block, over the copy threads */
+    uint8_t *bytes = (uint8_t *)buf->r;
+    struct copy_job *jobs = malloc((L->nb + 1) * sizeof(*jobs));
+    if (!jobs)
+        memcpy(bytes, h + L->o_hrng, L->packed);
+    size_t at = 0;
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        G->status[b] = hst[i];
+        G->out_len[b] = hol[i];
+        G->live[b] = hlv[i];
+        G->nranges[b] = hdn[i];
+        G->bytes[b] = hby[i];
+        G->err[b] = her[i];
+        G->dents[b] = bytes + at;
+        if (jobs) {
+            jobs[i].dst = bytes + at;
+            jobs[i].src = h + L->o_hrng + at;
+            jobs[i].len = hby[i];
+        }
+        at += hby[i];
+    }
+    if (jobs) {
+        copy_jobs(jobs, L->nb);
+        free(jobs);
+    }
+    pthread_mutex_lock(&G->mu);
+    buf->next = G->bufs;
+    G->bufs = buf;
+    pthread_mutex_unlock(&G->mu);
+    return 0;
+}
+
+/* ------------------------------------------------------------------------ */
 /* OP_COL_READ chunks: decode, region copy (col_slice.hip), slices back       */
 /* ------------------------------------------------------------------------ */
 /* A column and all its requests are in one chunk; request j of the chunk is
@@ -1405,7 +1569,8 @@ static int dev_run(void *arg, int d)
         /* walk chunks put their LZO blocks first (gc_partition): in a copy of the ids */
         const int gc = B->kind == OP_GC_SCAN;
         const int cr = B->kind == OP_COL_READ;
-        if (gc && !rev) {
+        const int rd = B->kind == OP_READDIR;
+        if ((gc || rd) && !rev) {
             if ((rev = malloc(nids * sizeof(*rev))) != NULL) {
                 memcpy(rev, ids, nids * sizeof(*rev));
                 ids = rev;
@@ -1446,7 +1611,7 @@ static int dev_run(void *arg, int d)
             if (dj >= 0) {
                 const int ahead = !B->ooo && live[nxt] && nxt != dj;
                 const int fail = fail_at >= 0 && ndeliv++ == fail_at;
-                if (fail || (gc ? gc_chunk_deliver : cr ? cr_chunk_deliver : chunk_deliver)(
+                if (fail || (gc ? gc_chunk_deliver : cr ? cr_chunk_deliver : rd ? rd_chunk_deliver : chunk_deliver)(
                                 &c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL, &L[nxt]) != 0) {
                     rc = -1;
                     for (int j = 0; j < B->nslots; j++)
@@ -1468,6 +1633,9 @@ static int dev_run(void *arg, int d)
                                    gc_partition(rev + from, end - from, B->gc->is_lzo), B->src_len, B->cap);
                 else if (cr)
                     cr_layout_make(&L[cur], ids + from, end - from, B);
+                else if (rd)
+                    rd_layout_make(&L[cur], ids + from, end - from,
+                                   gc_partition(rev + from, end - from, B->gc->is_lzo), B->src_len, B->cap);
                 else
                     layout_make(&L[cur], ids + from, end - from, B->src_len, B->cap,
                                 B->kind == OP_COMPRESS);
@@ -1475,7 +1643,8 @@ static int dev_run(void *arg, int d)
                  * while the chunks in flight are copied and decoded */
                 if (B->pre_chunk)
                     B->pre_chunk(B->cb_ctx, ids + from, end - from);
-                if ((gc ? gc_chunk_launch : cr ? cr_chunk_launch : chunk_launch)(&c->s[cur], &L[cur], B) != 0) {
+                if ((gc ? gc_chunk_launch : cr ? cr_chunk_launch : rd ? rd_chunk_launch : chunk_launch)(
+                        &c->s[cur], &L[cur], B) != 0) {
                     rc = -1;
                     hipStreamSynchronize(c->s[cur].stream);
                 } else {
@@ -1631,7 +1800,8 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
         rc = pom_run_devices(B.plan.ndev, dev_run, &B) == 0 ? LZO_E_OK : LZO_E_ERROR;
         if (g_timing)
             fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n",
-                    kind == OP_COMPRESS ? "compress" : gc ? "gc scan" : cr ? "column read" : "decompress", nblocks, B.plan.ndev,
+                    kind == OP_COMPRESS ? "compress" : kind == OP_READDIR ? "readdir" : gc ? "gc scan" : cr ? "column read" : "decompress",
+                    nblocks, B.plan.ndev,
                     now_ms() - t0);
         pom_plan_free(&B.plan);
     }
@@ -1648,6 +1818,16 @@ int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t
         sink->rng[b] = NULL;
     }
     return batch_common_cb(OP_GC_SCAN, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL);
+}
+
+int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                        struct pom_gc_sink *sink)
+{
+    for (size_t b = 0; b < nblocks; b++) {
+        sink->out_len[b] = sink->live[b] = sink->nranges[b] = sink->bytes[b] = 0;
+        sink->dents[b] = NULL;
+    }
+    return batch_common_cb(OP_READDIR, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL);
 }
 
 int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,

@@ -183,12 +183,44 @@ struct pom_gc_sink {
     int32_t *status, *err;
     uint32_t *out_len, *live, *nranges;
     const struct pom_gc_range **rng;
+    uint32_t *bytes;                /* pom_readdir_chunked only */
+    const uint8_t **dents;          /* pom_readdir_chunked only */
     struct pom_gc_buf *bufs;
     pthread_mutex_t mu;             /* bufs: chunks of a multi-GPU batch finish on several threads */
 };
 int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                         struct pom_gc_sink *sink);
 void pom_gc_sink_free(struct pom_gc_sink *sink);
+
+/* Host side (gc_scan.c), not part of the ABI: the header checks the walks'
+ * host batches share (include/pom_gc.h pom_gc_scan_batch).  0 and the block a
+ * record stands for -- its stored payload, whether that is an LZO1X stream,
+ * the decode capacity h.zlen - 264 (0 when stored uncompressed), adepth and
+ * h.entries -- or -EINVAL. */
+struct pom_walk_block {
+    const uint8_t *src;
+    size_t src_len, cap;
+    uint8_t is_lzo, adepth;
+    int32_t entries;
+};
+int pom_itb_walk_header(const uint8_t *rec, size_t rec_len, struct pom_walk_block *w);
+
+/* The directory listing's ITB walk (itb_dents.hip): pom_readdir_dev of
+ * include/pom_readdir.h, three launches on `stream`. */
+int lzo_mi355x_launch_readdir(const uint8_t *payload, const uint64_t *payload_off,
+                              const uint32_t *payload_len, const int32_t *status,
+                              const uint8_t *adepth, uint32_t nitb, uint32_t *live,
+                              uint32_t *dnum, uint32_t *bytes, uint64_t *first, uint8_t *out,
+                              uint64_t out_cap, int32_t *err, hipStream_t stream);
+
+/* Host side (lzo_host.c), not part of the ABI: pom_gc_scan_chunked's pipeline
+ * with the dentry walk in the range walk's place (readdir.c).  The sink is the
+ * same, read as follows: column and rng are unused, nranges[b] = the block's
+ * dnum, bytes[b] its record bytes, and dents[b] points at them, inside one of
+ * the per-chunk buffers linked at bufs.  Only the counts and the records are
+ * copied back. */
+int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                        struct pom_gc_sink *sink);
 
 /* Column reads by offset and size (col_slice.hip): pom_col_slice_dev of
  * include/pom_column.h, one launch on `stream`. */

@@ -63,6 +63,8 @@ EXPORTS = (
     "pom_xnet_itb_recv_batch",
     # include/pom_gc.h
     "pom_gc_scan_dev", "pom_gc_scan_batch",
+    # include/pom_readdir.h
+    "pom_readdir_dev", "pom_readdir_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
