@@ -29,6 +29,7 @@
 #include "pom_column.h"
 #include "pom_gc.h"
 #include "pom_readdir.h"
+#include "pom_lookup.h"
 
 /* Debug and experiment switches: ONE environment variable, POM_LZO_DEBUG,
  * a comma-separated list of key=value.  No product path
@@ -551,6 +552,7 @@ struct layout {
     /* OP_COL_READ chunks (cr_layout_make) */
     size_t nreq, res_hdr, res_bytes;
     size_t o_want, o_outoff, o_req, o_res, o_hres;
+    size_t o_names, names_bytes;    /* OP_LOOKUP chunks (lk_layout_make), which share fields of both */
 };
 
 static void layout_make(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
@@ -618,7 +620,7 @@ static void layout_fill(const struct layout *L, uint8_t *h, const uint8_t *const
     }
 }
 
-enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ, OP_READDIR };
+enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ, OP_READDIR, OP_LOOKUP };
 
 /* One host batch: the caller's arrays, the capacities the kernels use, and
  * the plan (device split, largest-first order). */
@@ -643,6 +645,7 @@ struct hbatch {
     void *cb_ctx;
     struct pom_gc_sink *gc; /* OP_GC_SCAN, OP_READDIR: the walk's per-block inputs and results */
     struct pom_col_sink *cr; /* OP_COL_READ: the columns' requests and their results */
+    struct pom_lookup_sink *lk; /* OP_LOOKUP: the ITBs' requests and their results */
 };
 
 /* debug key host_timing=1: per-batch and per-chunk wall times on stderr (diagnostic) */
@@ -1502,6 +1505,223 @@ static int cr_chunk_deliver(struct slot *S, struct layout *L, const struct hbatc
     return 0;
 }
 
+/* ------------------------------------------------------------------------ */
+/* OP_LOOKUP chunks: decode, chain walk (itb_find.hip), matched MDUs back     */
+/* ------------------------------------------------------------------------ */
+/* OP_GC_SCAN's partition (LZO records first, stored ones walked as staged)
+ * with OP_COL_READ's requests: an ITB and all its requests are in one chunk;
+ * request j of the chunk is the j-th in block order, then in the block's own
+ * order, renumbered to the chunk's ITB index, its name staged in a blob of the
+ * chunk's own.  A request whose name the caller's blob does not hold, or whose
+ * namelen is above 255, gets no name bytes and a name_off past the chunk's
+ * blob: the kernel's rule 4 refuses it, behind rules 1 to 3 as everywhere.
+ * Every result has a fixed size, so one copy of a known size brings them back,
+ * queued once the chunk's kernels are done (cr_chunk_collect says why).  The
+ * decoder's status reaches the host through the requests' err.  Staging (host
+ * and device alike up to the inputs' end):
+ *   [src_off u64][dst_off u64][scan_off u64][requests, nreq][src_len u32][dst_cap u32]
+ *   [status i32][out_len u32][adepth u8]
+ *   [src bytes, 16-B aligned per block][names]
+ *   device: [decoded payloads][decoder scratch]
+ *   both:   [err i32, nreq][nr u32, nreq][depth u32, nreq][records, 136 * nreq]  <- D2H, one copy
+ * No other decoded byte leaves the device. */
+static int lk_name_ok(const struct pom_lookup_sink *K, const struct pom_lookup_req *q)
+{
+    return q->namelen <= 255 && (size_t)q->name_off + q->namelen <= K->names_len;
+}
+
+static size_t lk_name_bytes(const struct pom_lookup_sink *K, const struct pom_lookup_req *q)
+{
+    return lk_name_ok(K, q) ? q->namelen : 0;
+}
+
+static void lk_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    const struct pom_lookup_sink *K = B->lk;
+    memset(L, 0, sizeof(*L));
+    L->nb = nb;
+    L->ids = ids;
+    L->nlzo = nlzo;
+    size_t s = 0, d = 0, nr = 0, nm = 0;
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = ids[i];
+        s += ALIGN_UP(B->src_len[b], 16);
+        if (i < nlzo)
+            d += ALIGN_UP(B->cap[b], 16);
+        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, nr++)
+            nm += lk_name_bytes(K, &K->req[K->req_ids[k]]);
+    }
+    L->nreq = nr;
+    L->names_bytes = nm;
+    size_t o = 0;
+    L->o_srcoff = o; o += 8 * nb;
+    L->o_dstoff = o; o += 8 * nb;
+    L->o_scanoff = o; o += 8 * nb;
+    L->o_req = o; o += sizeof(struct pom_lookup_req) * nr;
+    L->o_srclen = o; o += 4 * nb;
+    L->o_dstcap = o; o += 4 * nb;
+    L->o_status = o; o += 4 * nb;
+    L->o_outlen = o; o += 4 * nb;
+    L->o_adepth = o; o += nb;
+    o = ALIGN_UP(o, 256);
+    L->o_src = o;
+    o += ALIGN_UP(s, 256);
+    L->o_names = o;
+    o += ALIGN_UP(nm, 256);
+    L->o_dst = o;
+    L->res_hdr = ALIGN_UP(12 * nr, 16);
+    L->res_bytes = L->res_hdr + POM_LK_REC_SIZE * nr;
+    L->o_hres = o;
+    L->htotal = o + L->res_bytes;
+    o += ALIGN_UP(d, 256);
+    L->o_scr = o;
+    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
+    L->o_res = o;
+    L->dtotal = o + L->res_bytes;
+}
+
+static void lk_layout_fill(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    const struct pom_lookup_sink *K = B->lk;
+    uint64_t *so = (uint64_t *)(h + L->o_srcoff);
+    uint64_t *dof = (uint64_t *)(h + L->o_dstoff);
+    uint64_t *sco = (uint64_t *)(h + L->o_scanoff);
+    struct pom_lookup_req *rq = (struct pom_lookup_req *)(h + L->o_req);
+    uint32_t *sl = (uint32_t *)(h + L->o_srclen);
+    uint32_t *dc = (uint32_t *)(h + L->o_dstcap);
+    int32_t *st = (int32_t *)(h + L->o_status);
+    uint32_t *ol = (uint32_t *)(h + L->o_outlen);
+    uint8_t *ad = h + L->o_adepth;
+    uint8_t *nm = h + L->o_names;
+    size_t s = 0, d = 0, j = 0, at = 0;
+    struct copy_job *jobs = malloc(L->nb * sizeof(*jobs));
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        const int lzo = i < L->nlzo;
+        so[i] = s;
+        dof[i] = d;
+        sl[i] = (uint32_t)B->src_len[b];
+        dc[i] = lzo ? (uint32_t)B->cap[b] : 0;
+        /* the walk reads the decoders' status and out_len; a stored payload's are set here */
+        sco[i] = lzo ? L->o_dst + d : L->o_src + s;
+        st[i] = 0;
+        ol[i] = lzo ? 0 : (uint32_t)B->src_len[b];
+        ad[i] = K->adepth[b];
+        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
+            const struct pom_lookup_req *q = &K->req[K->req_ids[k]];
+            const size_t n = lk_name_bytes(K, q);
+            rq[j] = *q;
+            rq[j].itb = (uint32_t)i;            /* the chunk's own ITB index */
+            if (lk_name_ok(K, q)) {
+                rq[j].name_off = (uint32_t)at;
+                if (n)
+                    memcpy(nm + at, K->names + q->name_off, n);
+                at += n;
+            } else {
+                rq[j].name_off = 0xFFFFFFFFu;   /* outside the chunk's blob, as it was outside the caller's */
+            }
+        }
+        if (jobs) {
+            jobs[i].dst = h + L->o_src + s;
+            jobs[i].src = B->src[b];
+            jobs[i].len = B->src_len[b];
+        } else if (B->src_len[b]) {
+            memcpy(h + L->o_src + s, B->src[b], B->src_len[b]);
+        }
+        s += ALIGN_UP(B->src_len[b], 16);
+        d += ALIGN_UP((size_t)dc[i], 16);
+    }
+    if (jobs) {
+        copy_jobs(jobs, L->nb);
+        free(jobs);
+    }
+}
+
+/* As gc_chunk_launch: everything queued on the slot's stream, nothing waited for. */
+static int lk_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
+{
+    if (L->nreq > 0xFFFFFFFFu || L->names_bytes > 0xFFFFFFF0u || slot_reserve(S, L->dtotal, L->htotal) != 0)
+        return -1;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    hipStream_t s = S->stream;
+    const double t0 = g_timing ? now_ms() : 0;
+    lk_layout_fill(L, h, B);
+    if (g_timing)
+        fprintf(stderr, "  chunk n=%zu, %zu requests: fill %.2f ms (%zu B)\n", L->nb, L->nreq, now_ms() - t0, L->htotal);
+    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
+        return -1;
+    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
+    int32_t *st = (int32_t *)(d + L->o_status);
+    uint8_t *res = d + L->o_res;
+    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
+                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
+                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
+        lzo_mi355x_launch_lookup(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth,
+                                 (uint32_t)L->nb, (const struct pom_lookup_req *)(d + L->o_req),
+                                 (uint32_t)L->nreq, d + L->o_names, (uint32_t)L->names_bytes, (int32_t *)res,
+                                 (uint32_t *)(res + 4 * L->nreq), (uint32_t *)(res + 8 * L->nreq),
+                                 res + L->res_hdr, s) != 0)
+        return -1;
+    return 0;
+}
+
+/* As cr_chunk_collect: once the chunk's kernels are done, the one D2H of codes and records. */
+static int lk_chunk_collect(struct slot *S, struct layout *L, int poll)
+{
+    if (L->collected)
+        return 1;
+    hipStream_t s = S->stream;
+    if (poll) {
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady)
+            return 0;
+        if (q != hipSuccess)
+            return -1;
+    } else if (hipStreamSynchronize(s) != hipSuccess) {
+        return -1;
+    }
+    if (L->res_bytes && hipMemcpyAsync(S->hmem + L->o_hres, S->dmem + L->o_res, L->res_bytes,
+                                       hipMemcpyDeviceToHost, s) != hipSuccess)
+        return -1;
+    L->packed = L->res_bytes;
+    L->collected = 1;
+    return 1;
+}
+
+/* As cr_chunk_deliver: the results go to their places in the caller's request order. */
+static int lk_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
+                            struct slot *nS, struct layout *nL)
+{
+    const double t0 = g_timing ? now_ms() : 0;
+    if (lk_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
+        return -1;
+    if (nS && lk_chunk_collect(nS, nL, 0) < 0)
+        return -1;
+    const double t1 = g_timing ? now_ms() : 0;
+    struct pom_lookup_sink *K = B->lk;
+    const uint8_t *res = S->hmem + L->o_hres;
+    const int32_t *he = (const int32_t *)res;
+    const uint32_t *hn = (const uint32_t *)(res + 4 * L->nreq);
+    const uint32_t *hd = (const uint32_t *)(res + 8 * L->nreq);
+    const uint8_t *recs = res + L->res_hdr;
+    size_t j = 0;
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        K->status[b] = 0;                       /* delivered; the decoder's code is in the requests' err */
+        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
+            const size_t r = K->req_ids[k];
+            K->err[r] = he[j];
+            K->nr[r] = hn[j];
+            K->depth[r] = hd[j];
+            memcpy(K->out + POM_LK_REC_SIZE * r, recs + POM_LK_REC_SIZE * j, POM_LK_REC_SIZE);
+        }
+    }
+    if (g_timing)
+        fprintf(stderr, "  deliver n=%zu: wait %.2f (%zu B) unpack %.2f ms\n", L->nb, t1 - t0, L->packed,
+                now_ms() - t1);
+    return 0;
+}
+
 /* A host batch is cut into chunks of at most kChunkBudget bytes of input plus
  * output capacity (a larger block is a chunk of its own), pipelined through
  * the device's kSlots slots: chunk k is staged and its copies and kernels are
@@ -1570,7 +1790,8 @@ static int dev_run(void *arg, int d)
         const int gc = B->kind == OP_GC_SCAN;
         const int cr = B->kind == OP_COL_READ;
         const int rd = B->kind == OP_READDIR;
-        if ((gc || rd) && !rev) {
+        const int lk = B->kind == OP_LOOKUP;
+        if ((gc || rd || lk) && !rev) {
             if ((rev = malloc(nids * sizeof(*rev))) != NULL) {
                 memcpy(rev, ids, nids * sizeof(*rev));
                 ids = rev;
@@ -1611,7 +1832,8 @@ static int dev_run(void *arg, int d)
             if (dj >= 0) {
                 const int ahead = !B->ooo && live[nxt] && nxt != dj;
                 const int fail = fail_at >= 0 && ndeliv++ == fail_at;
-                if (fail || (gc ? gc_chunk_deliver : cr ? cr_chunk_deliver : rd ? rd_chunk_deliver : chunk_deliver)(
+                if (fail || (gc ? gc_chunk_deliver : cr ? cr_chunk_deliver : rd ? rd_chunk_deliver
+                                : lk ? lk_chunk_deliver : chunk_deliver)(
                                 &c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL, &L[nxt]) != 0) {
                     rc = -1;
                     for (int j = 0; j < B->nslots; j++)
@@ -1636,6 +1858,9 @@ static int dev_run(void *arg, int d)
                 else if (rd)
                     rd_layout_make(&L[cur], ids + from, end - from,
                                    gc_partition(rev + from, end - from, B->gc->is_lzo), B->src_len, B->cap);
+                else if (lk)
+                    lk_layout_make(&L[cur], ids + from, end - from,
+                                   gc_partition(rev + from, end - from, B->lk->is_lzo), B);
                 else
                     layout_make(&L[cur], ids + from, end - from, B->src_len, B->cap,
                                 B->kind == OP_COMPRESS);
@@ -1643,7 +1868,8 @@ static int dev_run(void *arg, int d)
                  * while the chunks in flight are copied and decoded */
                 if (B->pre_chunk)
                     B->pre_chunk(B->cb_ctx, ids + from, end - from);
-                if ((gc ? gc_chunk_launch : cr ? cr_chunk_launch : rd ? rd_chunk_launch : chunk_launch)(
+                if ((gc ? gc_chunk_launch : cr ? cr_chunk_launch : rd ? rd_chunk_launch
+                        : lk ? lk_chunk_launch : chunk_launch)(
                         &c->s[cur], &L[cur], B) != 0) {
                     rc = -1;
                     hipStreamSynchronize(c->s[cur].stream);
@@ -1704,12 +1930,12 @@ static int batch_devices(int *devs)
 static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                            uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
                            pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
-                           struct pom_gc_sink *gc, struct pom_col_sink *cr);
+                           struct pom_gc_sink *gc, struct pom_col_sink *cr, struct pom_lookup_sink *lk);
 
 static int batch_common(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                         uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks)
 {
-    return batch_common_cb(kind, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL, NULL, NULL);
+    return batch_common_cb(kind, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* lzo_mi355x_decompress_batch with pre_chunk(ctx, ids, nb) called before each
@@ -1720,7 +1946,7 @@ int pom_decompress_batch_chunked(const uint8_t *const *src, const size_t *src_le
                                  size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn pre_chunk,
                                  void *ctx)
 {
-    return batch_common_cb(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx, NULL, NULL);
+    return batch_common_cb(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx, NULL, NULL, NULL);
 }
 
 /* lzo_mi355x_compress_batch with on_chunk(ctx, ids, nb) called as each chunk's
@@ -1731,13 +1957,13 @@ int pom_compress_batch_chunked(const uint8_t *const *src, const size_t *src_len,
                                size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn on_chunk,
                                void *ctx)
 {
-    return batch_common_cb(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx, NULL, NULL);
+    return batch_common_cb(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx, NULL, NULL, NULL);
 }
 
 static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
                            uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
                            pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
-                           struct pom_gc_sink *gc, struct pom_col_sink *cr)
+                           struct pom_gc_sink *gc, struct pom_col_sink *cr, struct pom_lookup_sink *lk)
 {
     const double t0 = g_timing ? now_ms() : 0;
     struct tctx *t = tctx_get();
@@ -1765,17 +1991,21 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
             return LZO_E_ERROR;
         }
         cap[b] = kind == OP_COMPRESS ? lzo_mi355x_worst_compress(src_len[b]) : gc ? gc->cap[b]
-                 : cr ? (size_t)cr->want[b] : dst_len[b];
+                 : cr ? (size_t)cr->want[b] : lk ? lk->cap[b] : dst_len[b];
         if (cap[b] > 0xFFFFFFF0u)
             cap[b] = 0xFFFFFFF0u;
         cost[b] = src_len[b] + cap[b];
         if (cr)                                 /* the chunk budget counts the slices too */
             for (size_t k = cr->req_first[b]; k < cr->req_first[b + 1]; k++)
                 cost[b] += cr_slot(cr, b, k);
+        if (lk)                                 /* and the requests, their names and their results */
+            for (size_t k = lk->req_first[b]; k < lk->req_first[b + 1]; k++)
+                cost[b] += sizeof(struct pom_lookup_req) + 12 + POM_LK_REC_SIZE +
+                           lk_name_bytes(lk, &lk->req[lk->req_ids[k]]);
     }
     struct hbatch B = {kind, src, src_len, dst, dst_len, status, cap, cost,
                        kind == OP_COMPRESS ? kChunkBudgetCompress : kChunkBudget,
-                       {0, 1, NULL, NULL}, devs, t, 0, kSlots, 0, on_chunk, pre_chunk, cb_ctx, gc, cr};
+                       {0, 1, NULL, NULL}, devs, t, 0, kSlots, 0, on_chunk, pre_chunk, cb_ctx, gc, cr, lk};
     B.ooo = kind == OP_COMPRESS && pom_dbg_int("ooo", 1) != 0;
     /* compress chunks that fit the LDS encoder's 4 blocks per CU at once use
      * it: a block alone on its CU finishes twice as fast as with the
@@ -1794,13 +2024,13 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
             status[b] = LZO_E_ERROR;
             if (gc)
                 gc->err[b] = LZO_E_ERROR;
-            else if (!cr)                       /* (a column read's requests: set by the caller) */
+            else if (!cr && !lk)                /* (a column read's and a lookup's requests: set by the caller) */
                 dst_len[b] = 0;
         }
         rc = pom_run_devices(B.plan.ndev, dev_run, &B) == 0 ? LZO_E_OK : LZO_E_ERROR;
         if (g_timing)
             fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n",
-                    kind == OP_COMPRESS ? "compress" : kind == OP_READDIR ? "readdir" : gc ? "gc scan" : cr ? "column read" : "decompress",
+                    kind == OP_COMPRESS ? "compress" : kind == OP_READDIR ? "readdir" : lk ? "lookup" : gc ? "gc scan" : cr ? "column read" : "decompress",
                     nblocks, B.plan.ndev,
                     now_ms() - t0);
         pom_plan_free(&B.plan);
@@ -1817,7 +2047,7 @@ int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t
         sink->out_len[b] = sink->live[b] = sink->nranges[b] = 0;
         sink->rng[b] = NULL;
     }
-    return batch_common_cb(OP_GC_SCAN, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL);
+    return batch_common_cb(OP_GC_SCAN, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL, NULL);
 }
 
 int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
@@ -1827,14 +2057,21 @@ int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t
         sink->out_len[b] = sink->live[b] = sink->nranges[b] = sink->bytes[b] = 0;
         sink->dents[b] = NULL;
     }
-    return batch_common_cb(OP_READDIR, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL);
+    return batch_common_cb(OP_READDIR, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL, NULL);
 }
 
 int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                          struct pom_col_sink *sink)
 {
     return batch_common_cb(OP_COL_READ, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, NULL,
-                           sink);
+                           sink, NULL);
+}
+
+int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                       struct pom_lookup_sink *sink)
+{
+    return batch_common_cb(OP_LOOKUP, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, NULL,
+                           NULL, sink);
 }
 
 int lzo_mi355x_compress_batch(const uint8_t *const *src, const size_t *src_len,

@@ -252,6 +252,40 @@ struct pom_col_sink {
 int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                          struct pom_col_sink *sink);
 
+/* The lookup's ITB walk (itb_find.hip): pom_lookup_dev of
+ * include/pom_lookup.h, one launch on `stream`. */
+struct pom_lookup_req;
+int lzo_mi355x_launch_lookup(const uint8_t *payload, const uint64_t *payload_off,
+                             const uint32_t *payload_len, const int32_t *status,
+                             const uint8_t *adepth, uint32_t nitb, const struct pom_lookup_req *req,
+                             uint32_t nreq, const uint8_t *names, uint32_t names_len, int32_t *err,
+                             uint32_t *nr, uint32_t *depth, uint8_t *out, hipStream_t stream);
+
+/* Host side (lzo_host.c), not part of the ABI: pom_gc_scan_chunked's pipeline
+ * (LZO records decoded, stored ones walked as staged) with the lookup behind
+ * each chunk's decode and pom_col_read_chunked's request grouping (lookup.c).
+ * Block b's requests are req[req_ids[k]] for k in [req_first[b], req_first[b +
+ * 1]); an ITB and all its requests travel in one chunk, renumbered to the
+ * chunk's own ITB indices, with their names (from names[0, names_len)) staged
+ * behind them.  Per request err, nr, depth and the 136-byte record at out +
+ * 136 * r, all in the caller's request order; a decoder's code reaches the
+ * requests through err.  Only those come back. */
+struct pom_lookup_sink {
+    const uint8_t *is_lzo;
+    const size_t *cap;
+    const uint8_t *adepth;
+    const size_t *req_first, *req_ids;
+    const struct pom_lookup_req *req;
+    const uint8_t *names;
+    size_t names_len;
+    uint8_t *out;
+    int *err;
+    uint32_t *nr, *depth;
+    int32_t *status;
+};
+int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                       struct pom_lookup_sink *sink);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,8 @@ EXPORTS = (
     "pom_gc_scan_dev", "pom_gc_scan_batch",
     # include/pom_readdir.h
     "pom_readdir_dev", "pom_readdir_batch",
+    # include/pom_lookup.h
+    "pom_lookup_dev", "pom_lookup_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None

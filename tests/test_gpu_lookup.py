@@ -1,0 +1,315 @@
+"""GPU: the lookup (include/pom_lookup.h) against the Python restatement of
+mds/itb.c:1769-1814 in lookup_util.py -- pom_lookup_dev on guarded arenas,
+pom_lookup_batch through the host chunk pipeline.  err, nr, depth and all 136
+bytes of every record are compared."""
+from __future__ import annotations
+
+import struct
+
+import numpy as np
+import pytest
+
+import lookup_util as U
+from gpu_util import guarded_batch
+from pomegranate_amd import itb, lookup, lzo
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+H = itb.ITBH_SIZE
+FILL = 0x5A
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    d = torch.device("cuda:0")
+    torch.cuda.set_device(d)
+    return d
+
+
+@pytest.fixture(autouse=True)
+def _needs_gpu(dev):
+    """The host batches pick the device themselves; without one they skip too."""
+
+
+@pytest.fixture
+def debug_env(monkeypatch):
+    def set_(value):
+        monkeypatch.setenv("POM_LZO_DEBUG", value)      # (lzo_host.c pom_dbg_str)
+        lzo.debug_reload()
+    yield set_
+    monkeypatch.delenv("POM_LZO_DEBUG", raising=False)
+    lzo.debug_reload()
+
+
+@pytest.fixture(scope="module")
+def families():
+    """Every case family once, with its requests made and the oracle's answer
+    worked out: name -> (records, adepths, req, names, want)."""
+    fams = {}
+    for name, fam in (("mixed", U.family_mixed), ("chains", U.family_chains), ("handmade", U.family_handmade),
+                      ("states", U.family_states)):
+        recs, adepths, items = fam()
+        req, names = lookup.requests(items)
+        if name == "mixed":
+            req = req[np.random.default_rng(5).permutation(len(req))]
+        fams[name] = (recs, adepths, req, names)
+    fams["names"] = U.family_names()
+    return {k: v + (U.expect([U.payload_of(r) for r in v[0]], v[1], v[2], v[3]),) for k, v in fams.items()}
+
+
+def same(got, want):
+    for g, w, what in zip(got, want, ("err", "nr", "depth", "out")):
+        bad = np.flatnonzero((np.asarray(g) != w).reshape(len(w), -1).any(axis=1))
+        assert len(bad) == 0, f"{what}: request {int(bad[0])}: {g[bad[0]]} != {w[bad[0]]}"
+
+
+# ---------------------------------------------------------------------------
+# pom_lookup_dev on guarded arenas
+# ---------------------------------------------------------------------------
+class Outputs:
+    """err, nr, depth and out carved out of ONE arena of FILL bytes with guard
+    bytes around each, so a stray store shows; out starts at residue `oshift`
+    mod 16."""
+
+    def __init__(self, dev, nreq, oshift):
+        self.sizes = [("err", 4 * nreq), ("nr", 4 * nreq), ("depth", 4 * nreq), ("out", lookup.REC_SIZE * nreq)]
+        self.at, pos = {}, 4096
+        for name, nbytes in self.sizes:
+            if name == "out":
+                pos += oshift
+            self.at[name] = (pos, nbytes)
+            pos = (pos + nbytes + 4096 + 255) // 256 * 256
+        self.arena = torch.full((pos,), FILL, dtype=torch.uint8, device=dev)
+        assert self.arena.data_ptr() % 256 == 0 and self.at["out"][0] % 16 == oshift
+
+    def view(self, name, dtype=torch.uint8):
+        o, nbytes = self.at[name]
+        return self.arena[o: o + nbytes].view(dtype)
+
+    def results(self, nreq):
+        """(err, nr, depth, out) on the host, after checking that nothing
+        outside the four outputs changed."""
+        host = self.arena.cpu().numpy()
+        changed = host != FILL
+        for name, nbytes in self.sizes:
+            o = self.at[name][0]
+            changed[o: o + nbytes] = False
+        bad = np.flatnonzero(changed)
+        assert len(bad) == 0, f"{len(bad)} bytes changed outside the outputs, first at arena byte {int(bad[0])}"
+        cut = lambda name: host[self.at[name][0]: self.at[name][0] + self.at[name][1]]
+        return (cut("err").view(np.int32), cut("nr").view(np.uint32), cut("depth").view(np.uint32),
+                cut("out").reshape(nreq, lookup.REC_SIZE))
+
+
+def lookup_dev_once(dev, recs, adepths, req, names, shifts=None, nshift=0, oshift=0, status=None, continuation=None):
+    payloads = [U.payload_of(r) for r in recs]
+    shifts = [0] * len(recs) if shifts is None else shifts
+    src = guarded_batch(torch, payloads, dev, shifts, fill=0xEE,
+                        neighbours=None if continuation is None else "continuation", continuation=continuation)
+    blob = guarded_batch(torch, [bytes(names)], dev, [nshift], fill=0xEE)
+    nreq = len(req)
+    dreq = torch.from_numpy(np.ascontiguousarray(req).view(np.uint8).copy()).to(dev)
+    adepth = torch.tensor(adepths, dtype=torch.uint8, device=dev)
+    st = None if status is None else torch.tensor(status, dtype=torch.int32, device=dev)
+    out = Outputs(dev, nreq, oshift)
+    lookup.lookup_dev(src, adepth, dreq, nreq, blob.arena[int(blob.host_off[0]):], len(names),
+                      out.view("err", torch.int32), out.view("nr", torch.int32), out.view("depth", torch.int32),
+                      out.view("out"), status=st)
+    torch.cuda.synchronize()
+    return out.results(nreq)
+
+
+@pytest.mark.parametrize("family", ["mixed", "chains", "states"])
+def test_dev_families(dev, families, family):
+    """The mixed batch, the chains of 8 and of 1,024 hops and the ITE states:
+    payloads at residues of their own, the output aligned and at an odd
+    address -- the same bytes."""
+    recs, adepths, req, names, want = families[family]
+    shifts = [(3 * b + 1) % 16 for b in range(len(recs))]
+    same(lookup_dev_once(dev, recs, adepths, req, names, shifts, 5, 0), want)
+    same(lookup_dev_once(dev, recs, adepths, req, names, None, 0, 7), want)
+    assert (want[0] == 0).sum() > 30 and (want[0] == U.ENOENT).sum() >= 9
+    if family == "chains":
+        assert want[2].max() == 1024
+
+
+def test_dev_handmade_tables(dev, families):
+    """A: nothing past a UNIQUE slot that misses; B: OVERFLOW followed like
+    CONFLICT; C: conflict >= 2048 ends as a miss; D: a self-loop and a 2-cycle
+    return POM_LK_E_LOOP at depth 2048; E: an entry whose ITE ends past the
+    payload, and entry 32,767, are POM_GC_E_TRUNCATED for that request only --
+    with the cut ITE's missing byte right behind the payload."""
+    recs, adepths, req, names, want = families["handmade"]
+    whole = U.payload_of(recs[0])
+    got = lookup_dev_once(dev, recs, adepths, req, names, [0, 9], 2, 0, continuation=[b"", whole[-1:]])
+    same(got, want)
+    same(lookup_dev_once(dev, recs, adepths, req, names, [5, 0], 0, 3, continuation=[b"", whole[-1:]]), want)
+    err, _, depth, out = got
+    # (in the record one byte short the 2-cycle runs into the cut ITE 7 first)
+    assert (err == U.E_LOOP).sum() == 4 and (depth[err == U.E_LOOP] == 2048).all()
+    assert (err == U.E_TRUNCATED).sum() == 11 and (err == 0).sum() == 15
+    assert not out[err != 0].any()
+
+
+@pytest.mark.parametrize("shift", range(8))
+def test_dev_names_and_alignment(dev, families, shift):
+    """namelen 0, 1, 7, 8, 9, 16, 17 and 255 at every blob offset residue, the
+    blob and the payload themselves at residue `shift`; columns 0 ... 5 and
+    the refusals (column 6, stray flag bits, namelen 256, names outside the
+    blob)."""
+    recs, adepths, req, names, want = families["names"]
+    same(lookup_dev_once(dev, recs, adepths, req, names, [shift], shift, (5 * shift) % 16), want)
+    err = want[0]
+    assert (err == U.EINVAL).sum() == 15 and (err == 0).sum() == 78
+
+
+@pytest.mark.parametrize("nreq", [1, 2, 63, 64, 65, 129, 257])
+def test_dev_buffer_contract(dev, families, nreq):
+    """Whole and partial waves, odd and even counts (the span's last granule
+    is half a granule when the count is odd): the poison around err, nr, depth
+    and out stays, out at residues 0, 8 and 1 holds identical bytes, and the
+    failed requests' records are all zero."""
+    recs, adepths, req, names, want = families["mixed"]
+    pick = np.arange(nreq) * 3 % len(req)
+    sub = tuple(w[pick] for w in want)
+    assert (sub[0] != 0).any() or nreq < 3
+    outs = [lookup_dev_once(dev, recs, adepths, req[pick], names, None, 0, oshift) for oshift in (0, 8, 1)]
+    for got in outs:
+        same(got, sub)
+        assert not got[3][got[0] != 0].any()
+    assert (outs[0][3] == outs[1][3]).all() and (outs[0][3] == outs[2][3]).all()
+
+
+def test_dev_rule_order_status_and_itb_range(dev, families):
+    """itb >= nitb, then status, adepth, the index table's presence, then the
+    request's own checks; the other ITBs' requests are untouched."""
+    rec = families["chains"][0][0]
+    hsh, _, _, _, name = U.ite_fields(rec, U.H, 2)
+    good = dict(hash=hsh, flag=U.BY_NAME, name=name)
+    bad = dict(hash=hsh, flag=U.BY_NAME | 0x4, name=name)
+    req, names = lookup.requests([dict(itb=b, **q) for b in (0, 1, 2, 3, 4, 5, 0xFFFFFFFF) for q in (good, bad)])
+    short = bytearray(rec[: U.H + U.ITE_OFF - 1])
+    struct.pack_into("<I", short, itb.LEN_OFF, len(short))
+    recs, adepths, status = [rec, rec, rec, short, rec], [3, 3, 0, 3, 11], [0, -6, -5, 0, 0]
+    want = U.expect([U.payload_of(r) for r in recs], adepths, req, names, status)
+    same(lookup_dev_once(dev, recs, adepths, req, names, [1, 2, 3, 4, 5], 1, 0, status=status), want)
+    assert want[0].tolist() == [0, U.EINVAL, -6, -6, -5, -5, U.E_TRUNCATED, U.E_TRUNCATED] + [U.EINVAL] * 6
+
+
+def test_dev_many_requests_grid_stride(dev, families):
+    """600,000 requests over the mixed batch: more waves than the capped grid
+    holds (2,048 workgroups of 4), so the grid stride runs."""
+    recs, adepths, req, names, want = families["mixed"]
+    n = 600_000
+    pick = np.arange(n) % len(req)
+    got = lookup_dev_once(dev, recs, adepths, req[pick], names, None, 3, 0)
+    same(got, tuple(w[pick] for w in want))
+
+
+# ---------------------------------------------------------------------------
+# pom_lookup_batch against the oracle
+# ---------------------------------------------------------------------------
+def stored_mix(oracle, recs):
+    """COMPR_LZO and COMPR_NONE alternately."""
+    return [r if b % 3 == 1 else U.lzo_record(oracle, r) for b, r in enumerate(recs)]
+
+
+def test_batch_mixed(oracle, families):
+    """24 records, adepth 1 ... 10, LZO and stored, and one record no request
+    names (a stream that cannot be decoded: it is never uploaded); every live
+    entry by name and by uuid and the misses, shuffled."""
+    recs, adepths, req, names, want = families["mixed"]
+    stored = stored_mix(oracle, recs)
+    unnamed = U.lzo_record(oracle, recs[0])
+    unnamed[H + 5: H + 40] = bytes(35)
+    res = lookup.lookup_batch(stored + [unnamed], req, names)
+    same(res, want)
+
+
+@pytest.mark.parametrize("family", ["chains", "handmade", "states", "names"])
+def test_batch_families(oracle, families, family):
+    recs, adepths, req, names, want = families[family]
+    same(lookup.lookup_batch([U.lzo_record(oracle, r) for r in recs], req, names), want)
+    same(lookup.lookup_batch(recs, req, names), want)
+
+
+def test_batch_errors_stay_local(oracle, families):
+    """A malformed stream gives its requests the decoder's code, a bad adepth
+    and itb >= n give -EINVAL; the other ITBs' requests are unaffected."""
+    recs, adepths, req, names, want = families["mixed"]
+    stored = stored_mix(oracle, recs)
+    ln, zlen, _ = itb.header_fields(stored[2])
+    cut = bytearray(stored[2][: ln - 9])
+    struct.pack_into("<I", cut, itb.LEN_OFF, ln - 9)
+    rc, _ = oracle.decompress_safe(bytes(cut[H:]), zlen - H)
+    assert rc != 0
+    stored[2] = cut
+    stored[4] = bytearray(stored[4])
+    stored[4][3] = 11                                   # adepth
+    stored[5] = bytearray(stored[5])
+    stored[5][3] = 0
+    req = req.copy()
+    far = np.flatnonzero(req["itb"] == 9)
+    req["itb"][far[:3]] = [len(stored), len(stored) + 5, 0xFFFFFFFF]
+    err, nr, depth, out = (w.copy() for w in want)
+    for b, code in ((2, rc), (4, U.EINVAL), (5, U.EINVAL)):
+        err[req["itb"] == b] = code
+    err[far[:3]] = U.EINVAL
+    lost = err != want[0]
+    nr[lost], depth[lost], out[lost] = 0, 0, 0
+    assert lost.sum() > 60
+    same(lookup.lookup_batch(stored, req, names), (err, nr, depth, out))
+
+
+def test_batch_itbid_check_and_just_split(oracle, families):
+    """itbid_check: a hash whose bits above 10 do not select h.itbid is -ESPLIT
+    with depth 0 and no walk; a miss on a JUST_SPLIT record is -ESPLIT."""
+    a = U.make_record(7700, 8, 3, [0x400 * 5 + nr for nr in range(8)], depth=3, itbid=5)
+    b = U.make_record(7701, 8, 3, U.spread_hashes(77, 8), itb_flag=U.ITB_JUST_SPLIT)
+    items = U.hits_for(a, 0, range(8)) + U.hits_for(b, 1, range(8)) + U.misses_for(b, 1, 3) + U.misses_for(a, 0, 2)
+    wrong = dict(U.hits_for(a, 0, [1])[0])
+    wrong["hash"] ^= 0x400                              # itbid 4
+    items.append(wrong)
+    req, names = lookup.requests(items)
+    payloads = [U.payload_of(a), U.payload_of(b)]
+    err, nr, depth, out = U.expect(payloads, [3, 3], req, names)
+    err[(req["itb"] == 1) & (err == U.ENOENT)] = U.ESPLIT
+    stored = [U.lzo_record(oracle, a), b]
+    same(lookup.lookup_batch(stored, req, names), (err, nr, depth, out))
+    assert err[-1] == 0 and (err == U.ESPLIT).sum() >= 4
+    # with the check on: the last request and the uuid miss with the moved hash
+    # bit 40 (still itbid 5) ...
+    err2, nr2, depth2, out2 = err.copy(), nr.copy(), depth.copy(), out.copy()
+    err2[-1], nr2[-1], depth2[-1], out2[-1] = U.ESPLIT, 0, 0, 0
+    res = lookup.lookup_batch(stored, req, names, itbid_check=True)
+    same(res, (err2, nr2, depth2, out2))
+    # ... and an ITB all of whose requests fail the check is not decoded at all
+    only = req[-1:].copy()
+    damaged = bytearray(stored[0])
+    damaged[H + 5: H + 40] = bytes(35)
+    res = lookup.lookup_batch([damaged, b], only, names, itbid_check=True)
+    assert (res.err.tolist(), res.depth.tolist(), res.out.any()) == ([U.ESPLIT], [0], False)
+
+
+def test_batch_spans_chunks(oracle, families, debug_env, monkeypatch):
+    """chunk_mb=1: about 50 KB a record, so 60 records take several chunks, on
+    one GPU and on every visible one; the chunks reorder the blocks (smallest
+    first, LZO before stored) and the results still come in request order."""
+    recs, items = [], []
+    for b in range(60):
+        n_ites = 60 + 7 * (b % 9)
+        rec = U.make_record(7800 + b, n_ites, 8, U.spread_hashes(900 + b, n_ites))
+        recs.append(rec)
+        items += U.hits_for(rec, b, range(b % 4, n_ites, 4)) + U.misses_for(rec, b, b % n_ites)
+    req, names = lookup.requests(items)
+    req = req[np.random.default_rng(11).permutation(len(req))]
+    want = U.expect([U.payload_of(r) for r in recs], [8] * 60, req, names)
+    stored = [r if b % 4 == 1 else U.lzo_record(oracle, r) for b, r in enumerate(recs)]
+    debug_env("chunk_mb=1")
+    same(lookup.lookup_batch(stored, req, names), want)
+    monkeypatch.setenv("POM_LZO_DEVICES", "0")
+    same(lookup.lookup_batch(stored, req, names), want)
