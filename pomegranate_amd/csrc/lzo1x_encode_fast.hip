@@ -36,6 +36,7 @@
 
 #include "lzo_mi355x_kernels.h"
 #include "lzo1x_emit.h"
+#include "lzo1x_enc_rebase.h"
 #include "lzo1x_wave.h"
 
 namespace {
@@ -43,12 +44,14 @@ namespace {
 constexpr int kWave = 64;
 constexpr uint32_t kSlots = emit::kSlots;
 // Dictionary entries are u16: v = position - base + 1 (0 = empty).  Before a
-// window could store a value past 65535, the base moves up to a multiple of
-// kRebase at least kM4MaxOffset + 1 below the window, and every entry is
-// re-based: the ones below the new base are cleared -- their distance from
-// every later probe exceeds M4_MAX_OFFSET, so the reference rejects them too
-// (lib/minilzo.c:2878-2883) and the parse is unchanged.
-constexpr uint32_t kRebase = 8192;
+// window whose highest storable position would not fit (lzo1x_enc_rebase.h:
+// never in a block of up to 65,548 bytes), the base moves up to kM4MaxOffset
+// + 1 below the window, and every entry is re-based: the ones below the new
+// base are cleared -- their distance from every later probe exceeds
+// M4_MAX_OFFSET, so the reference rejects them too (lib/minilzo.c:2878-2883)
+// and the parse is unchanged.  Longer blocks re-base every 16,320 bytes or
+// more (rebase_dict below).
+static_assert(ENC_REBASE_BACK == 0xBFFF + 1 && ENC_REBASE_WINDOW == 64, "lzo1x_enc_rebase.h");
 constexpr uint32_t kMaxN = 1u << 24;            // larger blocks: the general encoder
 #ifndef POM_ENC_TOK
 #define POM_ENC_TOK 64
@@ -126,6 +129,7 @@ static_assert(sizeof(EncLdsT<true>) * POM_ENC_RESIDENT <= 160 * 1024, "LDS budge
 #define POM_ENC_PRIO_STEP 8192                  // one-wave kernel: wave priority steps down every this many input bytes left
 #endif
 typedef __attribute__((address_space(1))) uint16_t gu16;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <bool GD>
 struct Dict {
     uint16_t* lds;
@@ -158,21 +162,71 @@ struct Dict {
         else
             lds[slot] = (uint16_t)v;
     }
-    // entries 2i, 2i+1 of the table as one u32 (re-basing)
-    __device__ __forceinline__ uint32_t get2(uint32_t i) const
+    // (LDS) entries 2i, 2i+1 of the table as one u32
+    __device__ __forceinline__ void put2(uint32_t i, uint32_t v) const { ((uint32_t*)lds)[i] = v; }
+    // (GD, re-basing) entries 8c .. 8c+7 as four u32, read like get_if: from
+    // L2, so this wave's earlier puts show, and only if rd; stored only if wr
+    // (a buffer store out of range: dropped)
+    __device__ __forceinline__ u32x4 get8_if(uint32_t c, bool rd) const
     {
-        if (GD)
-            return __hip_atomic_load((uint32_t*)g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return ((uint32_t*)lds)[i];
+        return __builtin_amdgcn_raw_buffer_load_b128(rs, rd ? 16u * c : 0x80000000u, 0, 16);
     }
-    __device__ __forceinline__ void put2(uint32_t i, uint32_t v) const
+    __device__ __forceinline__ void put8_if(uint32_t c, u32x4 v, bool wr) const
     {
-        if (GD)
-            ((__attribute__((address_space(1))) uint32_t*)g)[i] = v;
-        else
-            ((uint32_t*)lds)[i] = v;
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, wr ? 16u * c : 0x80000000u, 0, 0);
     }
 };
+
+// Every entry moved down by delta, the ones at or below it cleared
+// (lzo1x_enc_rebase.h), 8 entries (16 bytes) per lane and step.
+//  * Global dictionary: DEPTH loads are in flight before the first is waited
+//    for -- 32 loads a lane in 32 / DEPTH round trips through L2.  While a lane
+//    holds its 8 entries it rewrites the byte of the written-slots bitmap that
+//    covers them: bit i stays set only if entry i is still not 0, so a cleared
+//    entry answers EMPTY without a load from here on (exact: 0 is what it now
+//    holds).  The new byte is ANDed with the old one: a slot this block never
+//    wrote stays clear whatever an earlier block left behind it.  A chunk
+//    whose byte is 0 is neither loaded nor stored.
+//  * LDS dictionary: b128 reads and writes.
+template <bool GD, int DEPTH>
+__device__ __forceinline__ void rebase_dict(const Dict<GD>& D, uint32_t delta, uint32_t l)
+{
+    constexpr uint32_t kChunks = kSlots / 8;
+    static_assert(kChunks % (DEPTH * kWave) == 0, "whole steps");
+    if (GD) {
+        uint8_t* occ8 = (uint8_t*)D.occ;             // (little endian: byte c = slots 8c .. 8c+7)
+        for (uint32_t c0 = l; c0 < kChunks; c0 += DEPTH * kWave) {
+            u32x4 v[DEPTH];
+            uint32_t ob[DEPTH];
+#pragma unroll
+            for (int k = 0; k < DEPTH; k++) {
+                ob[k] = occ8[c0 + k * kWave];
+                v[k] = D.get8_if(c0 + k * kWave, ob[k] != 0);
+            }
+#pragma unroll
+            for (int k = 0; k < DEPTH; k++) {
+                uint32_t w[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    w[i] = enc_rebase_pair(v[k][i], delta);
+                u32x4 nv = {w[0], w[1], w[2], w[3]};
+                D.put8_if(c0 + k * kWave, nv, ob[k] != 0);
+                occ8[c0 + k * kWave] = (uint8_t)(enc_rebase_live8(w) & ob[k]);
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): the stores are out before the next probe
+    } else {
+        u32x4* d4 = (u32x4*)D.lds;                   // (EncLdsT is 16-byte aligned, dict its first member)
+        for (uint32_t c = l; c < kChunks; c += kWave) {
+            const u32x4 v = d4[c];
+            u32x4 nv;
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                nv[i] = enc_rebase_pair(v[i], delta);
+            d4[c] = nv;
+        }
+    }
+}
 
 __device__ __forceinline__ uint32_t claim_index(uint32_t slot) { return (slot ^ (slot >> 9)) & (kClaim - 1); }
 
@@ -472,11 +526,13 @@ struct Emitter {
 // EP_CLAIM: the claim reads up to the first conflict mask; EP_FWDR: the
 // forwarding rounds after it.  EC_FALSE: flagged lanes with no writer.
 // EC_HWID, EC_XCC (one-wave kernel): the HW_ID and XCC_ID registers of the
-// wave that ran the block -- which CU of which XCD.
+// wave that ran the block -- which CU of which XCD.  EP_REBASE, EC_REBASE:
+// the dictionary re-bases (none in a block of up to 65,548 bytes).
 enum { EP_SETUP, EP_PROBE, EP_CAND, EP_PATH, EP_CLAIM, EP_TOK, EP_DICT, EP_PUSHWAIT,
        EC_WINDOWS, EC_EXTEND, EC_TOKENS, EC_PATHIT, EC_EXTIT, EC_C2NEED, EC_C2MATCH, EC_FWD,
-       EP_FWDR, EC_FALSE, EC_HWID, EC_XCC, EP_N };
+       EP_FWDR, EC_FALSE, EC_HWID, EC_XCC, EP_REBASE, EC_REBASE, EP_N };
 constexpr int kEncStampSlots = 24;
+static_assert(EP_N <= kEncStampSlots, "stamp slots");
 
 // FUSED (one-wave kernel): the parse wave runs the emitter E itself -- it
 // drains the token queue once POM_ENC_DRAIN tokens are pending (larger emit
@@ -568,20 +624,18 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                 }
                 prio_ip = q ? n - q * st + 1 : 0xFFFFFFFFu;     // left < q * st from there on
             }
-            if (ip + kWave - base >= 0xFFFFu) {     // this window's positions would not fit
-                const uint32_t nb = (ip - (kM4MaxOffset + 1)) / kRebase * kRebase;
-                const uint32_t delta = nb - base;
-                for (uint32_t s2 = l; s2 < kSlots / 2; s2 += kWave) {
-                    const uint32_t pr = D.get2(s2);
-                    const uint32_t lo = pr & 0xFFFFu, hi = pr >> 16;
-                    const uint32_t nlo = lo > delta ? lo - delta : 0u;
-                    const uint32_t nhi = hi > delta ? hi - delta : 0u;
-                    D.put2(s2, nlo | (nhi << 16));
-                }
-                if (GD)
-                    __builtin_amdgcn_s_waitcnt(0x0F70);
+            if (enc_rebase_due(ip, ip_end, base)) {  // this window's positions would not fit
+                const uint32_t nb = enc_rebase_target(ip);
+                ESTAMP(EP_DICT);
+                // (in flight per lane: 8 x 16 bytes in the one-wave kernel; 4 in
+                // the two-wave ones, which are capped at 64 VGPRs and spill --
+                // no more with 4 than without)
+                rebase_dict<GD, FUSED ? 8 : 4>(D, nb - base, l);
                 wave_order();
                 base = nb;
+                if (STAMPS)
+                    acc[EC_REBASE] += 1;
+                ESTAMP(EP_REBASE);
             }
             if (!FUSED && POM_ENC_AHEAD)
                 S.ip = ip;                          // (the emit wave reads ahead from here)

@@ -83,17 +83,21 @@ if fn is None or a.nostamps:
 phases = ["setup", "probe", "cand", "path", "claim", "tok", "dict", "pushwait"]
 counts = ["windows", "extend", "tokens", "pathit", "extit", "end_cross", "end_cap", "fwd"]
 # (slots 16..19: the forwarding rounds' cycles -- "claim" is the claim reads up
-# to the first conflict mask --, false alarms, and the HW_ID and XCC_ID registers)
-FWDR, FALSE, HWID, XCC = 16, 17, 18, 19
+# to the first conflict mask --, false alarms, and the HW_ID and XCC_ID registers;
+# slots 20, 21: the dictionary re-bases' cycles and their count -- 0 per block
+# up to 65,548 bytes)
+FWDR, FALSE, HWID, XCC, REBASE, NREBASE = 16, 17, 18, 19, 20, 21
 for name, t_ in (("lds", stamps), ("gdict", gstamps), ("gdict1", g1stamps)):
     st = t_.view(nb, SLOTS).double().cpu().numpy()
     cyc = {n: int(st[:, i].mean()) for i, n in enumerate(phases)}
     cyc["fwdrounds"] = int(st[:, FWDR].mean())
+    cyc["rebase"] = int(st[:, REBASE].mean())
     total = sum(cyc.values())
     print(name, "parse cycles/block (mean):", cyc, "total", total)
     print(name, "share of the chain (%):", {n: round(100.0 * v / max(total, 1), 1) for n, v in cyc.items()})
     cnt = {n: round(float(st[:, len(phases) + i].mean()), 1) for i, n in enumerate(counts)}
     cnt["false_alarm"] = round(float(st[:, FALSE].mean()), 1)
+    cnt["rebase"] = round(float(st[:, NREBASE].mean()), 2)
     print(name, "counts/block (mean):", cnt)
 # Where the one-wave kernel's blocks ran: HW_ID has cu_id in bits 11:8, sh_id in
 # bit 12 and se_id in bits 15:13; XCC_ID has the XCD in bits 3:0.
