@@ -45,8 +45,17 @@ extern "C" {
  * in[b] (kept uncompressed); otherwise tmp[b].zlen = tmp[b].len, tmp[b].len =
  * 264 + zlen, tmp[b].compress_algo = COMPR_LZO and oi[b] = tmp[b].  err[b] is
  * 0 or an LZO_E_* code (-EINVAL: h.len below the header size).
- * tmp_cap[b] is the size of tmp[b]; the output never exceeds it (the
- * reference writes past a full-size buffer on incompressible payloads).
+ * tmp_cap[b] is the size of tmp[b]; no byte at or past tmp[b] + tmp_cap[b] is
+ * written (the reference writes past a full-size buffer on incompressible
+ * payloads).  A record whose header and stream do not fit is kept uncompressed,
+ * as if compression had not paid (oi[b] = in[b], err[b] = 0; the column codec's
+ * rule, pom_column.h):
+ *   tmp_cap[b] < 264               tmp[b] is not touched at all;
+ *   tmp_cap[b] < 264 + stream      at most the 264 header bytes of tmp[b] are
+ *                                  written.
+ * A tmp[b] smaller than 264 + lzo_mi355x_worst_compress(h.len - 264) costs a
+ * side buffer and a copy (pomegranate_amd/csrc/itb_rules.h holds these rules).
+ * in[b] is never written.
  * Returns 0, or LZO_E_ERROR when the GPU path is unusable. */
 int pom_itb_lzo_compress_batch(uint8_t *const *in, uint8_t *const *tmp, const size_t *tmp_cap,
                                uint8_t **oi, int *err, size_t n);
@@ -56,7 +65,13 @@ int pom_itb_lzo_compress_batch(uint8_t *const *in, uint8_t *const *tmp, const si
  * reference's unchecked decoder has no bound).  err[b] = the decoder's LZO_E_*
  * code, as in the reference (an output length other than zlen - 264 is logged
  * there, not returned; it is reported here through len_ok[b] when non-NULL).
- * Always: compress_algo = COMPR_NONE, len = produced + 264. */
+ * Always: compress_algo = COMPR_NONE, len = produced + 264; with an error,
+ * produced is what the decoder had written when it stopped, and the bytes
+ * from 264 + produced to cap[b] are unspecified.
+ * Precondition: cap[b] >= 264 -- the header is read and rewritten whatever the
+ * payload does -- and in[b] holds the h.len bytes of the record (cap[b] below
+ * h.len only bounds the output).  No byte at or past in[b] + cap[b] is
+ * written. */
 int pom_itb_lzo_decompress_batch(uint8_t *const *in, const size_t *cap, int *err,
                                  int *len_ok, size_t n);
 

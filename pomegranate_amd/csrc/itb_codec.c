@@ -22,26 +22,20 @@
 #include <unistd.h>
 
 #include "io_util.h"
+#include "itb_rules.h"
 #include "lzo_mi355x.h"
 #include "minilzo.h"
 #include "pom_itb.h"
 #include "lzo_mi355x_kernels.h"
 
-static uint32_t rd32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-static void wr32(uint8_t *p, uint32_t v) { memcpy(p, &v, 4); }
-static void wr16(uint8_t *p, uint16_t v) { memcpy(p, &v, 2); }
+static uint32_t rd32(const uint8_t *p) { return itb_rules_rd32(p); }
 
 /* One itb_lzo_compress batch: the arrays of pom_itb_lzo_compress_batch, the
  * LZO batch's own, and (compress + append) the append file. */
 struct itb_wb {
     uint8_t *const *in;
     uint8_t *const *tmp;
+    const size_t *tmp_cap;
     uint8_t **oi;
     int *err;
     const uint8_t **src;
@@ -89,6 +83,7 @@ static int itb_wb_init(struct itb_wb *w, uint8_t *const *in, uint8_t *const *tmp
     memset(w, 0, sizeof(*w));
     w->in = in;
     w->tmp = tmp;
+    w->tmp_cap = tmp_cap;
     w->oi = oi;
     w->err = err;
     w->src = malloc(n * sizeof(*w->src));
@@ -101,41 +96,27 @@ static int itb_wb_init(struct itb_wb *w, uint8_t *const *in, uint8_t *const *tmp
         return LZO_E_OUT_OF_MEMORY;
     for (size_t b = 0; b < n; b++) {
         oi[b] = in[b];
-        const uint32_t len = rd32(in[b] + POM_ITBH_LEN_OFF);
-        w->slen[b] = len >= POM_ITBH_SIZE ? len - POM_ITBH_SIZE : 0;
+        w->slen[b] = itb_rules_payload_len(in[b]);
         w->src[b] = in[b] + POM_ITBH_SIZE;
-        w->dst[b] = tmp[b] + POM_ITBH_SIZE;
         const size_t worst = lzo_mi355x_worst_compress(w->slen[b]);
-        if (tmp_cap[b] < POM_ITBH_SIZE + worst) {
+        if (itb_rules_direct(tmp_cap[b], worst)) {
+            w->dst[b] = tmp[b] + POM_ITBH_SIZE;
+        } else {                                   /* never overrun the caller's buffer */
             w->aside[b] = malloc(worst);
             if (!w->aside[b])
                 return LZO_E_OUT_OF_MEMORY;
             w->dst[b] = w->aside[b];
         }
-        err[b] = len >= POM_ITBH_SIZE ? 0 : -EINVAL;
+        err[b] = rd32(in[b] + POM_ITBH_LEN_OFF) >= POM_ITBH_SIZE ? 0 : -EINVAL;
     }
     return LZO_E_OK;
 }
 
-/* mds/itb.c:2923-2944 for block b once its compressed bytes are in */
+/* mds/itb.c:2923-2944 for block b once its compressed bytes are in (itb_rules.h) */
 static void itb_wb_finish(struct itb_wb *w, size_t b)
 {
-    if (w->err[b])
-        return;
-    uint8_t *t = w->tmp[b];
-    memcpy(t, w->in[b], POM_ITBH_SIZE);                        /* the itb header */
-    if (w->st[b] != LZO_E_OK) {
-        w->err[b] = w->st[b];
-        return;
-    }
-    if (w->dlen[b] >= w->slen[b])                              /* impossible to compress */
-        return;
-    if (w->aside[b])
-        memcpy(t + POM_ITBH_SIZE, w->aside[b], w->dlen[b]);
-    wr32(t + POM_ITBH_ZLEN_OFF, rd32(t + POM_ITBH_LEN_OFF));
-    wr32(t + POM_ITBH_LEN_OFF, (uint32_t)(POM_ITBH_SIZE + w->dlen[b]));
-    wr16(t + POM_ITBH_ALGO_OFF, POM_COMPR_LZO);
-    w->oi[b] = t;
+    itb_rules_finish_compress(w->in[b], w->tmp[b], w->tmp_cap[b], w->dst[b], w->slen[b], w->dlen[b], w->st[b],
+                              &w->oi[b], &w->err[b]);
 }
 
 /* A chunk of the batch is compressed: finish its records and append them to
@@ -384,10 +365,8 @@ int pom_itb_lzo_decompress_batch(uint8_t *const *in, const size_t *cap, int *err
     int rc = LZO_E_OUT_OF_MEMORY;
     if (!src || !dst || !slen || !dlen || !st)
         goto out;
-    for (size_t b = 0; b < n; b++) {
-        const uint32_t len = rd32(in[b] + POM_ITBH_LEN_OFF);
-        slen[b] = len >= POM_ITBH_SIZE ? len - POM_ITBH_SIZE : 0;
-    }
+    for (size_t b = 0; b < n; b++)
+        slen[b] = itb_rules_payload_len(in[b]);
     /* in place: the batch call stages a block's payload before it writes that
      * block's output (include/lzo_mi355x.h), so no copy aside is needed */
     for (size_t b = 0; b < n; b++) {
@@ -398,14 +377,8 @@ int pom_itb_lzo_decompress_batch(uint8_t *const *in, const size_t *cap, int *err
     rc = lzo_mi355x_decompress_batch(src, slen, dst, dlen, st, n);
     if (rc != LZO_E_OK)
         goto out;
-    for (size_t b = 0; b < n; b++) {
-        const uint32_t zlen = rd32(in[b] + POM_ITBH_ZLEN_OFF);
-        err[b] = st[b];
-        if (len_ok)
-            len_ok[b] = st[b] == LZO_E_OK && dlen[b] + POM_ITBH_SIZE == zlen;
-        wr16(in[b] + POM_ITBH_ALGO_OFF, POM_COMPR_NONE);       /* clear the compress flag */
-        wr32(in[b] + POM_ITBH_LEN_OFF, (uint32_t)(dlen[b] + POM_ITBH_SIZE));
-    }
+    for (size_t b = 0; b < n; b++)
+        itb_rules_finish_decompress(in[b], st[b], dlen[b], &err[b], len_ok ? &len_ok[b] : NULL);
 out:
     free(src);
     free(dst);
@@ -858,13 +831,7 @@ int pom_itb_read_lzo_decompress_batch(int fd, const uint64_t *locations, size_t 
             len[b] = 0;                             /* buffer past the header is undefined */
             continue;
         }
-        const uint32_t zlen = rd32(buf[b] + POM_ITBH_ZLEN_OFF);
-        derr[b] = st[i];
-        if (len_ok)
-            len_ok[b] = st[i] == LZO_E_OK && dlen[i] + POM_ITBH_SIZE == zlen;
-        wr16(buf[b] + POM_ITBH_ALGO_OFF, POM_COMPR_NONE);
-        wr32(buf[b] + POM_ITBH_LEN_OFF, (uint32_t)(dlen[i] + POM_ITBH_SIZE));
-        len[b] = dlen[i] + POM_ITBH_SIZE;
+        len[b] = itb_rules_finish_decompress(buf[b], st[i], dlen[i], &derr[b], len_ok ? &len_ok[b] : NULL);
     }
 out:
     free(plen);

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "itb_rules.h"
 #include "lzo_mi355x.h"
 #include "lzo_mi355x_kernels.h"
 #include "minilzo.h"
@@ -20,12 +21,7 @@
 
 _Static_assert(sizeof(struct pom_xnet_tx) == POM_XNET_TX_SIZE, "struct xnet_msg_tx is 72 bytes");
 
-static uint32_t rd32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
+static uint32_t rd32(const uint8_t *p) { return itb_rules_rd32(p); }
 
 static uint16_t rd16(const uint8_t *p)
 {
@@ -232,12 +228,9 @@ int pom_xnet_itb_recv_batch(const struct pom_xnet_frame *f, size_t n, uint8_t *c
     if (rc != LZO_E_OK)
         goto out;
     for (size_t i = 0; i < nd; i++) {
-        uint8_t *h = itb[at[i]];
-        const uint16_t none = POM_COMPR_NONE;
-        const uint32_t nl = (uint32_t)(dlen[i] + POM_ITBH_SIZE);
-        memcpy(h + POM_ITBH_ALGO_OFF, &none, 2);      /* clear the compress flag */
-        memcpy(h + POM_ITBH_LEN_OFF, &nl, 4);
-        if (st[i] != LZO_E_OK)
+        int derr;
+        itb_rules_finish_decompress(itb[at[i]], st[i], dlen[i], &derr, NULL);
+        if (derr != LZO_E_OK)
             err[at[i]] = -EFAULT;                     /* itb_lzo_decompress failed */
     }
 out:
