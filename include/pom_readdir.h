@@ -13,10 +13,10 @@
  *   pom_readdir_batch  <- the same over stored records, decoded on the GPU
  *                         (records in host memory)
  *
- * The INDEX_KV branch (mds/itb.c:2472-2534: snprintf of keys, the strstr/regex
- * filter) and the INDEX_DTRIG triggers (itb_readdir_dtriggered) stay with the
- * caller, as do the reply's allocation and its zero tail (see
- * pom_readdir_batch).
+ * The INDEX_KV branch (mds/itb.c:2472-2534: "%ld" keys and the strstr filter;
+ * there is no regex on that path) is pom_kvlist.h's.  The INDEX_DTRIG triggers
+ * (itb_readdir_dtriggered) stay with the caller, as do the reply's allocation
+ * and its zero tail (see pom_readdir_batch).
  */
 #ifndef POM_READDIR_H
 #define POM_READDIR_H 1

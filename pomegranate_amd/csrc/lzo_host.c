@@ -30,6 +30,7 @@
 #include "pom_gc.h"
 #include "pom_readdir.h"
 #include "pom_lookup.h"
+#include "pom_kvlist.h"
 
 /* Debug and experiment switches: ONE environment variable, POM_LZO_DEBUG,
  * a comma-separated list of key=value.  No product path
@@ -553,6 +554,8 @@ struct layout {
     size_t nreq, res_hdr, res_bytes;
     size_t o_want, o_outoff, o_req, o_res, o_hres;
     size_t o_names, names_bytes;    /* OP_LOOKUP chunks (lk_layout_make), which share fields of both */
+    /* OP_KVLIST chunks (kv_layout_make), which share OP_READDIR's fields */
+    size_t o_keybytes, o_needle, o_mask, o_hmask;
 };
 
 static void layout_make(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
@@ -620,7 +623,7 @@ static void layout_fill(const struct layout *L, uint8_t *h, const uint8_t *const
     }
 }
 
-enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ, OP_READDIR, OP_LOOKUP };
+enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ, OP_READDIR, OP_LOOKUP, OP_KVLIST };
 
 /* One host batch: the caller's arrays, the capacities the kernels use, and
  * the plan (device split, largest-first order). */
@@ -643,7 +646,7 @@ struct hbatch {
     pom_chunk_fn on_chunk;  /* called with each delivered chunk's block ids, or NULL */
     pom_chunk_fn pre_chunk; /* called with a chunk's block ids before its inputs are staged */
     void *cb_ctx;
-    struct pom_gc_sink *gc; /* OP_GC_SCAN, OP_READDIR: the walk's per-block inputs and results */
+    struct pom_gc_sink *gc; /* OP_GC_SCAN, OP_READDIR, OP_KVLIST: the walk's per-block inputs and results */
     struct pom_col_sink *cr; /* OP_COL_READ: the columns' requests and their results */
     struct pom_lookup_sink *lk; /* OP_LOOKUP: the ITBs' requests and their results */
 };
@@ -1291,6 +1294,192 @@ static int rd_chunk_deliver(struct slot *S, struct layout *L, const struct hbatc
 }
 
 /* ------------------------------------------------------------------------ */
+/* OP_KVLIST chunks: decode, key walk (itb_keys.hip), counts and records back */
+/* ------------------------------------------------------------------------ */
+/* OP_READDIR's chunks with the key walk in the dentry walk's place: the same
+ * partition and fill; a keybytes word per block and the call's needle, staged
+ * once per chunk, are added, the emit masks stay on the device unless the
+ * caller asked for them, and a count-only call has no records.  Staging:
+ *   [src_off u64][dst_off u64][scan_off u64][first u64, nb + 1][src_len u32][dst_cap u32]
+ *   [status i32][out_len u32][live u32][dnum u32][bytes u32][keybytes u32][err i32]   <- D2H, one copy
+ *   [adepth u8]
+ *   [needle, 256 bytes]
+ *   [src bytes, 16-B aligned per block]
+ *   host:   [masks, 128 bytes per block, when asked for]         <- D2H behind the counts
+ *           [the chunk's records, unless count-only]             <- D2H, sized after the first
+ *   device: [decoded payloads][decoder scratch][masks][records, 324 bytes for every ITE the payloads can hold]
+ * No other decoded byte leaves the device. */
+static void kv_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    const size_t *src_len = B->src_len, *cap = B->cap;
+    memset(L, 0, sizeof(*L));
+    L->nb = nb;
+    L->ids = ids;
+    L->nlzo = nlzo;
+    size_t o = 0;
+    L->o_srcoff = o; o += 8 * nb;
+    L->o_dstoff = o; o += 8 * nb;
+    L->o_scanoff = o; o += 8 * nb;
+    L->o_first = o; o += 8 * (nb + 1);
+    L->o_srclen = o; o += 4 * nb;
+    L->o_dstcap = o; o += 4 * nb;
+    L->o_status = o; o += 4 * nb;
+    L->o_outlen = o; o += 4 * nb;
+    L->o_live = o; o += 4 * nb;
+    L->o_nranges = o; o += 4 * nb;
+    L->o_bytes = o; o += 4 * nb;
+    L->o_keybytes = o; o += 4 * nb;
+    L->o_err = o; o += 4 * nb;
+    L->o_adepth = o; o += nb;
+    o = ALIGN_UP(o, 256);
+    L->o_needle = o; o += 256;
+    L->o_src = o;
+    size_t s = 0, d = 0, r = 0;
+    for (size_t i = 0; i < nb; i++) {
+        s += ALIGN_UP(src_len[ids[i]], 16);
+        if (i < nlzo)
+            d += ALIGN_UP(cap[ids[i]], 16);
+        r += gc_max_ranges(i < nlzo ? cap[ids[i]] : src_len[ids[i]]) * (4 + POM_KV_VALUE_MAX);
+    }
+    const size_t masks = ALIGN_UP(8 * POM_KV_MASK_WORDS * nb, 256);
+    L->rcap = r;
+    o += ALIGN_UP(s, 256);
+    L->o_dst = o;
+    L->o_hmask = o;
+    L->o_hrng = o + (B->gc->mask ? masks : 0);
+    L->htotal = L->o_hrng + (B->gc->count_only ? 0 : r);
+    o += ALIGN_UP(d, 256);
+    L->o_scr = o;
+    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
+    L->o_mask = o;
+    o += masks;
+    L->o_pack = o;
+    L->dtotal = o + r;
+}
+
+/* As rd_chunk_launch. */
+static int kv_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
+{
+    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
+        return -1;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    hipStream_t s = S->stream;
+    const uint32_t nb = (uint32_t)L->nb;
+    const struct pom_gc_sink *G = B->gc;
+    gc_layout_fill(L, h, B);
+    memset(h + L->o_needle, 0, 256);
+    if (G->needle_len)
+        memcpy(h + L->o_needle, G->needle, G->needle_len);
+    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
+        return -1;
+    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
+    int32_t *st = (int32_t *)(d + L->o_status);
+    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
+                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
+                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
+        lzo_mi355x_launch_kvlist(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth, nb,
+                                 G->kv_op, d + L->o_needle, G->needle_len,
+                                 (uint32_t *)(d + L->o_live), (uint32_t *)(d + L->o_nranges),
+                                 (uint32_t *)(d + L->o_bytes), (uint32_t *)(d + L->o_keybytes),
+                                 (uint64_t *)(d + L->o_mask), (uint64_t *)(d + L->o_first),
+                                 d + L->o_pack, G->count_only ? 0 : L->rcap, (int32_t *)(d + L->o_err), s) != 0)
+        return -1;
+    if (hipMemcpyAsync(h + L->o_status, d + L->o_status, 28 * L->nb, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return -1;
+    if (G->mask && hipMemcpyAsync(h + L->o_hmask, d + L->o_mask, 8 * POM_KV_MASK_WORDS * L->nb,
+                                  hipMemcpyDeviceToHost, s) != hipSuccess)
+        return -1;
+    return 0;
+}
+
+/* As rd_chunk_collect; a count-only chunk has nothing more to fetch. */
+static int kv_chunk_collect(struct slot *S, struct layout *L, const struct hbatch *B, int poll)
+{
+    if (L->collected)
+        return 1;
+    hipStream_t s = S->stream;
+    if (poll) {
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady)
+            return 0;
+        if (q != hipSuccess)
+            return -1;
+    } else if (hipStreamSynchronize(s) != hipSuccess) {
+        return -1;
+    }
+    size_t total = 0;
+    if (!B->gc->count_only) {
+        const uint32_t *hby = (const uint32_t *)(S->hmem + L->o_bytes);
+        for (size_t i = 0; i < L->nb; i++)
+            total += hby[i];
+        if (total > L->rcap)
+            return -1;
+        if (total && hipMemcpyAsync(S->hmem + L->o_hrng, S->dmem + L->o_pack, total, hipMemcpyDeviceToHost, s) !=
+                         hipSuccess)
+            return -1;
+    }
+    L->packed = total;
+    L->collected = 1;
+    return 1;
+}
+
+/* As rd_chunk_deliver. */
+static int kv_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
+                            struct slot *nS, struct layout *nL)
+{
+    if (kv_chunk_collect(S, L, B, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
+        return -1;
+    if (nS && kv_chunk_collect(nS, nL, B, 0) < 0)
+        return -1;
+    struct pom_gc_sink *G = B->gc;
+    const uint8_t *h = S->hmem;
+    const int32_t *hst = (const int32_t *)(h + L->o_status);
+    const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
+    const uint32_t *hlv = (const uint32_t *)(h + L->o_live);
+    const uint32_t *hdn = (const uint32_t *)(h + L->o_nranges);
+    const uint32_t *hby = (const uint32_t *)(h + L->o_bytes);
+    const uint32_t *hkb = (const uint32_t *)(h + L->o_keybytes);
+    const int32_t *her = (const int32_t *)(h + L->o_err);
+    struct pom_gc_buf *buf = malloc(sizeof(*buf) + L->packed);
+    if (!buf)
+        return -1;
+    uint8_t *bytes = (uint8_t *)buf->r;
+    struct copy_job *jobs = malloc((L->nb + 1) * sizeof(*jobs));
+    if (!jobs)
+        memcpy(bytes, h + L->o_hrng, L->packed);
+    size_t at = 0;
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        const size_t nbytes = G->count_only ? 0 : hby[i];
+        G->status[b] = hst[i];
+        G->out_len[b] = hol[i];
+        G->live[b] = hlv[i];
+        G->nranges[b] = hdn[i];
+        G->bytes[b] = hby[i];
+        G->keybytes[b] = hkb[i];
+        G->err[b] = her[i];
+        G->dents[b] = G->count_only ? NULL : bytes + at;
+        if (G->mask)
+            memcpy(G->mask + POM_KV_MASK_WORDS * b, h + L->o_hmask + 8 * POM_KV_MASK_WORDS * i, 8 * POM_KV_MASK_WORDS);
+        if (jobs) {
+            jobs[i].dst = bytes + at;
+            jobs[i].src = h + L->o_hrng + at;
+            jobs[i].len = nbytes;
+        }
+        at += nbytes;
+    }
+    if (jobs) {
+        copy_jobs(jobs, L->nb);
+        free(jobs);
+    }
+    pthread_mutex_lock(&G->mu);
+    buf->next = G->bufs;
+    G->bufs = buf;
+    pthread_mutex_unlock(&G->mu);
+    return 0;
+}
+
+/* ------------------------------------------------------------------------ */
 /* OP_COL_READ chunks: decode, region copy (col_slice.hip), slices back       */
 /* ------------------------------------------------------------------------ */
 /* A column and all its requests are in one chunk; request j of the chunk is
@@ -1791,7 +1980,8 @@ static int dev_run(void *arg, int d)
         const int cr = B->kind == OP_COL_READ;
         const int rd = B->kind == OP_READDIR;
         const int lk = B->kind == OP_LOOKUP;
-        if ((gc || rd || lk) && !rev) {
+        const int kv = B->kind == OP_KVLIST;
+        if ((gc || rd || lk || kv) && !rev) {
             if ((rev = malloc(nids * sizeof(*rev))) != NULL) {
                 memcpy(rev, ids, nids * sizeof(*rev));
                 ids = rev;
@@ -1833,7 +2023,7 @@ static int dev_run(void *arg, int d)
                 const int ahead = !B->ooo && live[nxt] && nxt != dj;
                 const int fail = fail_at >= 0 && ndeliv++ == fail_at;
                 if (fail || (gc ? gc_chunk_deliver : cr ? cr_chunk_deliver : rd ? rd_chunk_deliver
-                                : lk ? lk_chunk_deliver : chunk_deliver)(
+                                : lk ? lk_chunk_deliver : kv ? kv_chunk_deliver : chunk_deliver)(
                                 &c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL, &L[nxt]) != 0) {
                     rc = -1;
                     for (int j = 0; j < B->nslots; j++)
@@ -1861,6 +2051,9 @@ static int dev_run(void *arg, int d)
                 else if (lk)
                     lk_layout_make(&L[cur], ids + from, end - from,
                                    gc_partition(rev + from, end - from, B->lk->is_lzo), B);
+                else if (kv)
+                    kv_layout_make(&L[cur], ids + from, end - from,
+                                   gc_partition(rev + from, end - from, B->gc->is_lzo), B);
                 else
                     layout_make(&L[cur], ids + from, end - from, B->src_len, B->cap,
                                 B->kind == OP_COMPRESS);
@@ -1869,7 +2062,7 @@ static int dev_run(void *arg, int d)
                 if (B->pre_chunk)
                     B->pre_chunk(B->cb_ctx, ids + from, end - from);
                 if ((gc ? gc_chunk_launch : cr ? cr_chunk_launch : rd ? rd_chunk_launch
-                        : lk ? lk_chunk_launch : chunk_launch)(
+                        : lk ? lk_chunk_launch : kv ? kv_chunk_launch : chunk_launch)(
                         &c->s[cur], &L[cur], B) != 0) {
                     rc = -1;
                     hipStreamSynchronize(c->s[cur].stream);
@@ -2030,7 +2223,7 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
         rc = pom_run_devices(B.plan.ndev, dev_run, &B) == 0 ? LZO_E_OK : LZO_E_ERROR;
         if (g_timing)
             fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n",
-                    kind == OP_COMPRESS ? "compress" : kind == OP_READDIR ? "readdir" : lk ? "lookup" : gc ? "gc scan" : cr ? "column read" : "decompress",
+                    kind == OP_COMPRESS ? "compress" : kind == OP_READDIR ? "readdir" : kind == OP_KVLIST ? "kvlist" : lk ? "lookup" : gc ? "gc scan" : cr ? "column read" : "decompress",
                     nblocks, B.plan.ndev,
                     now_ms() - t0);
         pom_plan_free(&B.plan);
@@ -2058,6 +2251,16 @@ int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t
         sink->dents[b] = NULL;
     }
     return batch_common_cb(OP_READDIR, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL, NULL);
+}
+
+int pom_kvlist_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                       struct pom_gc_sink *sink)
+{
+    for (size_t b = 0; b < nblocks; b++) {
+        sink->out_len[b] = sink->live[b] = sink->nranges[b] = sink->bytes[b] = sink->keybytes[b] = 0;
+        sink->dents[b] = NULL;
+    }
+    return batch_common_cb(OP_KVLIST, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL, NULL);
 }
 
 int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,

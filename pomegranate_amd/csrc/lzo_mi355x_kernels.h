@@ -185,6 +185,12 @@ struct pom_gc_sink {
     const struct pom_gc_range **rng;
     uint32_t *bytes;                /* pom_readdir_chunked only */
     const uint8_t **dents;          /* pom_readdir_chunked only */
+    /* pom_kvlist_chunked only: */
+    uint32_t *keybytes;
+    uint64_t *mask;                 /* 16 words a block, or NULL: the masks stay on the device */
+    uint32_t kv_op, needle_len;
+    const uint8_t *needle;
+    int count_only;                 /* no emit launch, no record comes back */
     struct pom_gc_buf *bufs;
     pthread_mutex_t mu;             /* bufs: chunks of a multi-GPU batch finish on several threads */
 };
@@ -221,6 +227,25 @@ int lzo_mi355x_launch_readdir(const uint8_t *payload, const uint64_t *payload_of
  * copied back. */
 int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                         struct pom_gc_sink *sink);
+
+/* The key/value table listing's ITB walk (itb_keys.hip): pom_kvlist_dev of
+ * include/pom_kvlist.h, three launches on `stream`. */
+int lzo_mi355x_launch_kvlist(const uint8_t *payload, const uint64_t *payload_off,
+                             const uint32_t *payload_len, const int32_t *status,
+                             const uint8_t *adepth, uint32_t nitb, uint32_t op, const uint8_t *needle,
+                             uint32_t needle_len, uint32_t *live, uint32_t *dnum, uint32_t *bytes,
+                             uint32_t *keybytes, uint64_t *mask, uint64_t *first, uint8_t *out,
+                             uint64_t out_cap, int32_t *err, hipStream_t stream);
+
+/* Host side (lzo_host.c), not part of the ABI: pom_readdir_chunked's pipeline
+ * with the key walk in the dentry walk's place (kvlist.c).  The sink is read
+ * as pom_readdir_chunked reads it (nranges[b] = the block's dnum, bytes[b] its
+ * record bytes, dents[b] points at them), plus keybytes[b], the masks when
+ * mask is given, and the call's op and needle, which is staged once per
+ * chunk.  With count_only no record is emitted or copied back (dents[b] stays
+ * NULL).  Only the counts, the masks asked for and the records come back. */
+int pom_kvlist_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                       struct pom_gc_sink *sink);
 
 /* Column reads by offset and size (col_slice.hip): pom_col_slice_dev of
  * include/pom_column.h, one launch on `stream`. */

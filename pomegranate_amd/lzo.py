@@ -67,6 +67,8 @@ EXPORTS = (
     "pom_readdir_dev", "pom_readdir_batch",
     # include/pom_lookup.h
     "pom_lookup_dev", "pom_lookup_batch",
+    # include/pom_kvlist.h
+    "pom_kvlist_dev", "pom_kvlist_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
