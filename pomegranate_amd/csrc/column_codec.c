@@ -3,7 +3,7 @@
  * the host-resident LZO1X batch API.  Format and fallback follow
  * api/api.c:6509-6541, :6652-6689 and :6427-6446; reads by offset and size
  * (:6447-6460) go through the host batches' pipeline with the region copy
- * behind each chunk's decode (lzo_host.c, OP_COL_READ; the rules are
+ * behind each chunk's decode (host_records.c, cr_ops; the rules are
  * col_slice.h's).
  */
 #include <stdlib.h>

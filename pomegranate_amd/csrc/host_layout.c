@@ -1,0 +1,168 @@
+/* host_layout.c -- the staging layouts of host_layout.h: plain arithmetic, no
+ * HIP.  Each builder lays the arrays out in the order its operation's staging
+ * diagram gives (lzo_host.c for the codec, host_records.c for the others). */
+#include <string.h>
+
+#include "host_layout.h"
+#include "pom_column.h"
+#include "pom_kvlist.h"
+#include "pom_lookup.h"
+
+size_t pom_walk_max_ites(size_t n)
+{
+    const size_t ites = n > POM_ITB_ITE_OFF ? (n - POM_ITB_ITE_OFF) / POM_ITE_SIZE : 0;
+    return ites < 1024 ? ites : 1024;
+}
+
+/* The next `bytes` of the staging: their offset. */
+static size_t take(size_t *o, size_t bytes)
+{
+    const size_t at = *o;
+    *o += bytes;
+    return at;
+}
+
+/* What every layout starts from; the inputs' and the output slots' sizes. */
+static void layout_start(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                         const size_t *cap, size_t *in_bytes, size_t *out_bytes)
+{
+    memset(L, 0, sizeof(*L));
+    L->nb = nb;
+    L->ids = ids;
+    L->nlzo = nlzo;
+    size_t s = 0, d = 0;
+    for (size_t i = 0; i < nb; i++) {
+        s += POM_ALIGN_UP(src_len[ids[i]], 16);
+        if (i < nlzo)
+            d += POM_ALIGN_UP(cap[ids[i]], 16);
+    }
+    *in_bytes = POM_ALIGN_UP(s, 256);
+    *out_bytes = POM_ALIGN_UP(d, 256);
+}
+
+void pom_layout_codec(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
+                      const size_t *cap, size_t scratch)
+{
+    size_t in, out, o = 0;
+    layout_start(L, ids, nb, nb, src_len, cap, &in, &out);
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    L->u.codec.res_off = o;
+    L->o_outlen = take(&o, 4 * nb);
+    L->o_status = take(&o, 4 * nb);
+    L->u.codec.res_bytes = o - L->u.codec.res_off;
+    L->u.codec.o_poff = take(&o, 8 * nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    L->o_dst = take(&o, out);
+    L->htotal = o;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    L->u.codec.o_pack = take(&o, out);
+    L->dtotal = o;
+}
+
+void pom_layout_walk(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                     const size_t *cap, const struct walk_spec *W, size_t scratch)
+{
+    size_t in, out, o = 0, r = 0;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct walk_layout *K = &L->u.walk;
+    for (size_t i = 0; i < nb; i++)
+        r += pom_walk_max_ites(i < nlzo ? cap[ids[i]] : src_len[ids[i]]) * W->per_ite;
+    const size_t masks = W->masks ? POM_ALIGN_UP(8 * POM_KV_MASK_WORDS * nb, 256) : 0;
+    K->rcap = r;
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    K->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_first = take(&o, 8 * (nb + 1));
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    K->res_off = o;
+    for (size_t w = 0; w < W->nwords; w++)
+        K->o_word[W->words[w]] = take(&o, 4 * nb);
+    K->res_bytes = o - K->res_off;
+    L->o_status = K->o_word[WW_STATUS];
+    L->o_outlen = K->o_word[WW_OUTLEN];
+    K->scan.o_adepth = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    K->o_needle = take(&o, W->needle ? 256 : 0);
+    L->o_src = take(&o, in);
+    L->o_dst = o;
+    K->o_hmask = o;
+    K->o_hrec = o + (W->host_masks ? masks : 0);
+    L->htotal = K->o_hrec + (W->host_records ? r : 0);
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_mask = take(&o, masks);
+    K->o_pack = take(&o, r);
+    L->dtotal = o;
+}
+
+void pom_layout_col(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
+                    const size_t *cap, size_t nreq, size_t slice_bytes, size_t scratch)
+{
+    size_t in, out, o = 0, r = 0;
+    layout_start(L, ids, nb, nb, src_len, cap, &in, &out);
+    struct col_layout *C = &L->u.col;
+    C->nreq = nreq;
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    C->o_want = take(&o, 8 * nb);
+    C->o_outoff = take(&o, 8 * nreq);
+    C->o_req = take(&o, sizeof(struct pom_col_req) * nreq);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    L->o_dst = o;
+    C->r_status = take(&r, 4 * nb);
+    C->r_outlen = take(&r, 4 * nb);
+    C->r_len = take(&r, 4 * nreq);
+    C->r_err = take(&r, 4 * nreq);
+    C->res_hdr = POM_ALIGN_UP(r, 16);
+    C->res_bytes = C->res_hdr + slice_bytes;
+    C->o_hres = o;
+    L->htotal = o + C->res_bytes;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    C->o_res = take(&o, C->res_bytes);
+    L->o_status = C->o_res + C->r_status;
+    L->o_outlen = C->o_res + C->r_outlen;
+    L->dtotal = o;
+}
+
+void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                       const size_t *cap, size_t nreq, size_t names_bytes, size_t scratch)
+{
+    size_t in, out, o = 0, r = 0;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct lookup_layout *K = &L->u.lk;
+    K->nreq = nreq;
+    K->names_bytes = names_bytes;
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    K->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_req = take(&o, sizeof(struct pom_lookup_req) * nreq);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    L->o_status = take(&o, 4 * nb);
+    L->o_outlen = take(&o, 4 * nb);
+    K->scan.o_adepth = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    K->o_names = take(&o, POM_ALIGN_UP(names_bytes, 256));
+    L->o_dst = o;
+    K->r_err = take(&r, 4 * nreq);
+    K->r_nr = take(&r, 4 * nreq);
+    K->r_depth = take(&r, 4 * nreq);
+    K->res_hdr = POM_ALIGN_UP(r, 16);
+    K->res_bytes = K->res_hdr + POM_LK_REC_SIZE * nreq;
+    K->o_hres = o;
+    L->htotal = o + K->res_bytes;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_res = take(&o, K->res_bytes);
+    L->dtotal = o;
+}

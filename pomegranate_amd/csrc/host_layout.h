@@ -1,0 +1,134 @@
+/* host_layout.h -- where everything lies in the staging of one chunk of a host
+ * batch (internal to liblzo_mi355x.so; plain C, no HIP, so that
+ * tests/native/layout_check.c checks the arithmetic on the CPU).
+ *
+ * A chunk's staging is one region of pinned host memory and one of device
+ * memory, laid out alike from byte 0 to the end of the inputs, so that one
+ * H2D copy of [0, o_dst) brings up everything the kernels read.  What lies
+ * behind differs per side and per operation.  Block i of the chunk is the
+ * caller's block ids[i]; blocks [0, nlzo) are LZO1X streams the decoders run
+ * over, the others are stored payloads that ride along and are walked where
+ * they are staged (codec and column chunks: nlzo = nb).
+ */
+#ifndef POM_HOST_LAYOUT_H
+#define POM_HOST_LAYOUT_H 1
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define POM_ALIGN_UP(x, a) (((x) + (size_t)(a) - 1) & ~((size_t)(a) - 1))
+
+/* Codec chunks: the kernels write each block into its capacity-sized dst slot;
+ * only the produced bytes come back, packed (pack kernel), in one D2H copy
+ * into the host's dst region. */
+struct codec_layout {
+    size_t res_off, res_bytes;  /* out_len and status: the D2H behind the kernels */
+    size_t o_poff;              /* u64 per block: its place among the packed bytes */
+    size_t o_pack;              /* device only: the packed output */
+};
+
+/* Operations whose kernel walks payloads where they lie: decoded, or stored
+ * uncompressed and staged among the inputs. */
+struct scan_layout {
+    size_t o_scanoff;           /* u64 per block: the payload's offset in the device staging */
+    size_t o_adepth;            /* u8 per block */
+};
+
+/* The per-block result words of the walks (u32 or i32 each).  An operation
+ * names the ones it has, in staging order (struct walk_spec); they lie one
+ * array behind the other and come back in one D2H copy. */
+enum walk_word { WW_STATUS, WW_OUTLEN, WW_LIVE, WW_COUNT, WW_BYTES, WW_KEYBYTES, WW_ERR, WW_N };
+
+struct walk_spec {
+    const uint8_t *words;       /* enum walk_word, in staging order */
+    size_t nwords;
+    size_t per_ite;             /* bytes of record room per ITE a payload can hold */
+    size_t unit;                /* the records' unit: 16 (ranges, WW_COUNT of them) or 1 (bytes, WW_BYTES of them) */
+    int needle;                 /* a 256-byte needle is staged with the inputs */
+    int masks;                  /* emit masks, 128 bytes per block, on the device ... */
+    int host_masks;             /* ... and copied back */
+    int host_records;           /* the records are copied back (not count-only) */
+};
+
+struct walk_layout {
+    struct scan_layout scan;
+    size_t o_first;             /* u64, nb + 1 */
+    size_t o_word[WW_N];        /* the result words the operation has */
+    size_t res_off, res_bytes;  /* their span: the D2H behind the kernels */
+    size_t o_needle;
+    size_t rcap;                /* record room, in bytes */
+    size_t o_mask, o_pack;      /* device only: masks, records */
+    size_t o_hmask, o_hrec;     /* host only: masks, records */
+};
+
+/* Column reads.  The results -- a header of four arrays, then the slices --
+ * lie alike on both sides (device o_res, host o_hres) and come back in one
+ * copy; the r_ offsets are relative to the results' start. */
+struct col_layout {
+    size_t nreq;
+    size_t o_want;              /* u64 per block */
+    size_t o_outoff;            /* u64 per request: its slice's place among the slices */
+    size_t o_req;               /* struct pom_col_req per request */
+    size_t o_res, o_hres;
+    size_t r_status, r_outlen;  /* i32, u32 per block */
+    size_t r_len, r_err;        /* u32, i32 per request */
+    size_t res_hdr, res_bytes;  /* the slices start at res_hdr; the whole is res_bytes */
+};
+
+/* Lookups.  As col_layout: a header of three arrays, then the 136-byte records. */
+struct lookup_layout {
+    struct scan_layout scan;
+    size_t nreq, names_bytes;
+    size_t o_req;               /* struct pom_lookup_req per request */
+    size_t o_names;             /* the chunk's own name blob, behind the inputs */
+    size_t o_res, o_hres;
+    size_t r_err, r_nr, r_depth;    /* i32, u32, u32 per request */
+    size_t res_hdr, res_bytes;
+};
+
+struct layout {
+    size_t nb;
+    const size_t *ids;
+    size_t nlzo;
+    int collected;              /* the D2H behind the kernels is queued */
+    size_t packed;              /* its bytes */
+    size_t o_srcoff, o_dstoff;  /* u64 per block */
+    size_t o_srclen, o_dstcap;  /* u32 per block */
+    size_t o_outlen, o_status;  /* u32, i32 per block: the decoders' results, on the device */
+    size_t o_src;               /* the blocks' input bytes, each 16-byte aligned */
+    size_t o_dst;               /* end of the H2D; on the device the output (or decoded payload) slots */
+    size_t o_scr;               /* device only: scratch of the kernels */
+    size_t htotal, dtotal;
+    union {
+        struct codec_layout codec;
+        struct walk_layout walk;
+        struct col_layout col;
+        struct lookup_layout lk;
+    } u;
+};
+
+/* src_len[] and cap[] are indexed by the caller's block ids; a block behind
+ * nlzo takes no output slot.  scratch: bytes of device scratch the chunk's
+ * kernels need (the encoder's or the decoders', for the blocks they run over). */
+void pom_layout_codec(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
+                      const size_t *cap, size_t scratch);
+void pom_layout_walk(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                     const size_t *cap, const struct walk_spec *W, size_t scratch);
+/* slice_bytes: the requests' clamped lengths, each rounded up to 16 */
+void pom_layout_col(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
+                    const size_t *cap, size_t nreq, size_t slice_bytes, size_t scratch);
+void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                       const size_t *cap, size_t nreq, size_t names_bytes, size_t scratch);
+
+/* The ITEs a payload of n bytes can hold: what a walk can emit at the most. */
+size_t pom_walk_max_ites(size_t n);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -5,7 +5,7 @@
  * itbid check and the JUST_SPLIT miss) and the grouping of the requests by
  * ITB are here; the chunks -- compressed payloads, requests and names up, the
  * decoders, the chain walk (itb_find.hip), codes and records back in request
- * order -- go through the host batches' pipeline (lzo_host.c, OP_LOOKUP).
+ * order -- go through the host batches' pipeline (host_records.c, lk_ops).
  */
 #include <errno.h>
 #include <stdlib.h>

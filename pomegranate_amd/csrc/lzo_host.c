@@ -22,15 +22,9 @@
 
 #include <hip/hip_runtime_api.h>
 
-#include "batch_split.h"
+#include "host_pipeline.h"
 #include "lzo_mi355x.h"
-#include "lzo_mi355x_kernels.h"
 #include "minilzo.h"
-#include "pom_column.h"
-#include "pom_gc.h"
-#include "pom_readdir.h"
-#include "pom_lookup.h"
-#include "pom_kvlist.h"
 
 /* Debug and experiment switches: ONE environment variable, POM_LZO_DEBUG,
  * a comma-separated list of key=value.  No product path
@@ -99,7 +93,7 @@ long pom_dbg_int(const char *key, long dflt)
     return v && *v ? atol(v) : dflt;
 }
 
-#define ALIGN_UP(x, a) (((x) + (size_t)(a) - 1) & ~((size_t)(a) - 1))
+#define ALIGN_UP(x, a) POM_ALIGN_UP(x, a)
 
 /* ------------------------------------------------------------------------ */
 /* GPU availability (checked once per process)                              */
@@ -132,15 +126,6 @@ size_t lzo_mi355x_worst_compress(size_t n)
 /* ------------------------------------------------------------------------ */
 /* Per-thread, per-device streams and staging                               */
 /* ------------------------------------------------------------------------ */
-/* A staging slot: one stream with its device and pinned host buffers (grown
- * on demand; a host batch's chunks keep them bounded, see kChunkBudget). */
-struct slot {
-    hipStream_t stream;
-    uint8_t *dmem;
-    size_t dcap;
-    uint8_t *hmem;
-    size_t hcap;
-};
 
 /* A host thread's resources on one device: kSlots slots, so that several
  * chunks are in flight (copies and kernels of some while others are packed
@@ -455,12 +440,6 @@ int lzo_mi355x_decoded_length_dev(const uint8_t *src, const uint64_t *src_off,
 /* Pack/unpack copies between caller buffers and the pinned staging: split
  * over up to kCopyThreads threads by bytes once a batch is large enough for
  * one memcpy stream to be the bottleneck (the host side of config C5). */
-struct copy_job {
-    uint8_t *dst;
-    const uint8_t *src;
-    size_t len;
-};
-
 struct copy_range {
     const struct copy_job *jobs;
     size_t lo, hi;
@@ -478,7 +457,7 @@ static void *copy_worker(void *arg)
     return NULL;
 }
 
-static void copy_jobs(const struct copy_job *jobs, size_t n)
+void pom_copy_jobs(const struct copy_job *jobs, size_t n)
 {
     size_t total = 0;
     for (size_t i = 0; i < n; i++)
@@ -526,12 +505,12 @@ void pom_copy_parallel(uint8_t *const *dst, const uint8_t *const *src, const siz
         jobs[i].src = src[i];
         jobs[i].len = len[i];
     }
-    copy_jobs(jobs, n);
+    pom_copy_jobs(jobs, n);
     free(jobs);
 }
 
-/* Staging layout of one chunk (identical on host and device, so one copy each
- * way):
+/* Staging layout of one codec chunk (identical on host and device, so one copy
+ * each way; pom_layout_codec):
  *   [src_off u64][dst_off u64][src_len u32][dst_cap u32][out_len u32][status i32]
  *   [packed offset u64]
  *   [src bytes, 16-B aligned per block][dst bytes, 16-B aligned per block]
@@ -539,61 +518,7 @@ void pom_copy_parallel(uint8_t *const *dst, const uint8_t *const *src, const siz
  * The kernels write each block into its capacity-sized dst slot; only the
  * produced bytes come back, packed (pack kernel), in one D2H copy into the
  * host's dst region.  Block i of the chunk is the caller's block ids[i]. */
-struct layout {
-    size_t nb;
-    const size_t *ids;
-    int collected;          /* produced bytes packed and their D2H queued */
-    size_t packed;
-    size_t o_srcoff, o_dstoff, o_srclen, o_dstcap, o_outlen, o_status, o_poff;
-    size_t o_src, o_dst, o_scr, o_pack, htotal, dtotal;
-    /* OP_GC_SCAN chunks (gc_layout_make) */
-    size_t nlzo, rcap;
-    size_t o_scanoff, o_first, o_live, o_nranges, o_err, o_adepth, o_hrng;
-    size_t o_bytes;         /* OP_READDIR chunks (rd_layout_make), which share the fields above */
-    /* OP_COL_READ chunks (cr_layout_make) */
-    size_t nreq, res_hdr, res_bytes;
-    size_t o_want, o_outoff, o_req, o_res, o_hres;
-    size_t o_names, names_bytes;    /* OP_LOOKUP chunks (lk_layout_make), which share fields of both */
-    /* OP_KVLIST chunks (kv_layout_make), which share OP_READDIR's fields */
-    size_t o_keybytes, o_needle, o_mask, o_hmask;
-};
-
-static void layout_make(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
-                        const size_t *dst_cap, int compress)
-{
-    L->nb = nb;
-    L->ids = ids;
-    L->collected = 0;
-    L->packed = 0;
-    size_t o = 0;
-    L->o_srcoff = o; o += 8 * nb;
-    L->o_dstoff = o; o += 8 * nb;
-    L->o_srclen = o; o += 4 * nb;
-    L->o_dstcap = o; o += 4 * nb;
-    L->o_outlen = o; o += 4 * nb;
-    L->o_status = o; o += 4 * nb;
-    L->o_poff = o; o += 8 * nb;
-    o = ALIGN_UP(o, 256);
-    L->o_src = o;
-    size_t s = 0, d = 0;
-    for (size_t i = 0; i < nb; i++) {
-        s += ALIGN_UP(src_len[ids[i]], 16);
-        d += ALIGN_UP(dst_cap[ids[i]], 16);
-    }
-    o += ALIGN_UP(s, 256);
-    L->o_dst = o;
-    o += ALIGN_UP(d, 256);
-    L->htotal = o;
-    L->o_scr = o;
-    /* scratch of the one kernel family the batch runs */
-    o += ALIGN_UP(compress ? lzo_mi355x_compress_scratch((uint32_t)nb)
-                           : lzo_mi355x_decompress_scratch((uint32_t)nb), 256);
-    L->o_pack = o;
-    L->dtotal = o + ALIGN_UP(d, 256);
-}
-
-static void layout_fill(const struct layout *L, uint8_t *h, const uint8_t *const *src,
-                        const size_t *src_len, const size_t *dst_cap)
+int pom_stage_inputs(const struct layout *L, uint8_t *h, const struct hbatch *B)
 {
     uint64_t *so = (uint64_t *)(h + L->o_srcoff);
     uint64_t *dof = (uint64_t *)(h + L->o_dstoff);
@@ -605,51 +530,24 @@ static void layout_fill(const struct layout *L, uint8_t *h, const uint8_t *const
         const size_t b = L->ids[i];
         so[i] = s;
         dof[i] = d;
-        sl[i] = (uint32_t)src_len[b];
-        dc[i] = (uint32_t)dst_cap[b];
+        sl[i] = (uint32_t)B->src_len[b];
+        dc[i] = i < L->nlzo ? (uint32_t)B->cap[b] : 0;
         if (jobs) {
             jobs[i].dst = h + L->o_src + s;
-            jobs[i].src = src[b];
-            jobs[i].len = src_len[b];
-        } else if (src_len[b]) {
-            memcpy(h + L->o_src + s, src[b], src_len[b]);
+            jobs[i].src = B->src[b];
+            jobs[i].len = B->src_len[b];
+        } else if (B->src_len[b]) {
+            memcpy(h + L->o_src + s, B->src[b], B->src_len[b]);
         }
-        s += ALIGN_UP(src_len[b], 16);
-        d += ALIGN_UP(dst_cap[b], 16);
+        s += ALIGN_UP(B->src_len[b], 16);
+        d += ALIGN_UP((size_t)dc[i], 16);
     }
     if (jobs) {
-        copy_jobs(jobs, L->nb);
+        pom_copy_jobs(jobs, L->nb);
         free(jobs);
     }
+    return 0;
 }
-
-enum op_kind { OP_COMPRESS, OP_DECOMPRESS, OP_CONCAT, OP_GC_SCAN, OP_COL_READ, OP_READDIR, OP_LOOKUP, OP_KVLIST };
-
-/* One host batch: the caller's arrays, the capacities the kernels use, and
- * the plan (device split, largest-first order). */
-struct hbatch {
-    enum op_kind kind;
-    const uint8_t *const *src;
-    const size_t *src_len;
-    uint8_t *const *dst;
-    size_t *dst_len;
-    int *status;
-    const size_t *cap;
-    const size_t *cost;
-    size_t budget;
-    struct pom_plan plan;
-    const int *devs;        /* plan device d runs on HIP device devs[d] */
-    struct tctx *t;
-    uint32_t enc_lds_max;   /* chunks of at most this many blocks: LDS dictionaries */
-    int nslots;             /* chunks in flight per device (<= kSlots) */
-    int ooo;                /* deliver chunks in completion order (compress batches) */
-    pom_chunk_fn on_chunk;  /* called with each delivered chunk's block ids, or NULL */
-    pom_chunk_fn pre_chunk; /* called with a chunk's block ids before its inputs are staged */
-    void *cb_ctx;
-    struct pom_gc_sink *gc; /* OP_GC_SCAN, OP_READDIR, OP_KVLIST: the walk's per-block inputs and results */
-    struct pom_col_sink *cr; /* OP_COL_READ: the columns' requests and their results */
-    struct pom_lookup_sink *lk; /* OP_LOOKUP: the ITBs' requests and their results */
-};
 
 /* debug key host_timing=1: per-batch and per-chunk wall times on stderr (diagnostic) */
 #define g_timing (pom_dbg_int("host_timing", 0) == 1)
@@ -734,7 +632,7 @@ static int use_lat_decoder(size_t z);
  * these few blocks; lzo1x_decode_lat.hip) with the exact decoder behind it for
  * the blocks it hands over.  1 launched, 0 not eligible (nothing launched),
  * -1 on an error. */
-static int lat_chunk(struct slot *S, const struct layout *L, const uint8_t *h, uint8_t *d, hipStream_t s)
+static int lat_chunk(const struct layout *L, const uint8_t *h, uint8_t *d, hipStream_t s)
 {
     const uint32_t nb = (uint32_t)L->nb;
     if (nb == 0 || nb > 8)
@@ -746,7 +644,6 @@ static int lat_chunk(struct slot *S, const struct layout *L, const uint8_t *h, u
     for (uint32_t i = 0; i < nb; i++)
         if (!use_lat_decoder(sl[i]))
             return 0;
-    (void)S;
     const size_t need = lzo_mi355x_decompress_lat_scratch_n(so, sl, dc, nb);
     if (need == 0 || need > kLatMaxScratch)
         return 0;
@@ -771,116 +668,141 @@ static int lat_chunk(struct slot *S, const struct layout *L, const uint8_t *h, u
     return 1;
 }
 
-/* Chunk on slot S: inputs into pinned staging, H2D, kernels, D2H of the
- * lengths -- all queued on the slot's stream, nothing waited for. */
-static int chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
+/* The chunk's blocks as the kernels take them: pointers into the device staging. */
+struct dev_blocks {
+    const uint8_t *src;
+    uint8_t *dst;
+    const uint64_t *so, *dof;
+    const uint32_t *sl, *dc;
+    uint32_t *ol;
+    int32_t *st;
+};
+
+static struct dev_blocks dev_blocks(const struct slot *S, const struct layout *L)
 {
-    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
-        return -1;
-    uint8_t *d = S->dmem, *h = S->hmem;
-    hipStream_t s = S->stream;
-    const uint32_t nb = (uint32_t)L->nb;
-    const double t0 = g_timing ? now_ms() : 0;
-    layout_fill(L, h, B->src, B->src_len, B->cap);
-    if (g_timing)
-        fprintf(stderr, "  chunk n=%u: fill %.2f ms (%zu B)\n", nb, now_ms() - t0, L->htotal);
-    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
-        return -1;
-    const uint8_t *dsrc = d + L->o_src;
-    uint8_t *ddst = d + L->o_dst;
-    const uint64_t *so = (const uint64_t *)(d + L->o_srcoff);
-    const uint64_t *dof = (const uint64_t *)(d + L->o_dstoff);
-    const uint32_t *sl = (const uint32_t *)(d + L->o_srclen);
-    const uint32_t *dc = (const uint32_t *)(d + L->o_dstcap);
-    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
-    int32_t *st = (int32_t *)(d + L->o_status);
-    int rc;
-    if (B->kind == OP_COMPRESS) {
-        /* lzo_mi355x_compress_dev, with the general encoder's pass only when a
-         * block of the chunk needs it: that kernel's workgroups take 64 KB of
-         * LDS each, and behind the other slots' encoders a pass with nothing to
-         * do waited ~0.75 ms for LDS to free up (C5 trace) */
-        void *scr = nb <= B->enc_lds_max ? NULL : d + L->o_scr;
-        int big = 0;
-        for (size_t i = 0; i < L->nb; i++)
-            big |= B->src_len[L->ids[i]] > LZO_MI355X_FAST_MAX_N;
-        rc = lzo_mi355x_launch_compress_fast(dsrc, so, sl, ddst, dof, dc, ol, st, nb, scr,
-                                             scr ? lzo_mi355x_compress_scratch(nb) : 0, s);
-        if (rc == 0 && big)
-            rc = lzo_mi355x_launch_compress(dsrc, so, sl, ddst, dof, dc, ol, st, nb, 1, s);
-    }
-    else if (B->kind == OP_DECOMPRESS) {
-        const int lat = lat_chunk(S, L, h, d, s);
-        rc = lat < 0 ? -1 : lat > 0 ? 0 : decompress_dev(dsrc, so, sl, ddst, dof, dc, ol, st, nb, d + L->o_scr, 0, s);
-    }
-    else
-        rc = lzo_mi355x_launch_decompress_concat(dsrc, so, sl, ddst, dof, dc, ol, st, nb, s);
-    if (rc != 0)
-        return -1;
-    return hipMemcpyAsync(h + L->o_outlen, d + L->o_outlen, 8 * L->nb, hipMemcpyDeviceToHost, s) ==
-                   hipSuccess ? 0 : -1;
+    uint8_t *d = S->dmem;
+    const struct dev_blocks D = {d + L->o_src, d + L->o_dst, (const uint64_t *)(d + L->o_srcoff),
+                                 (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_srclen),
+                                 (const uint32_t *)(d + L->o_dstcap), (uint32_t *)(d + L->o_outlen),
+                                 (int32_t *)(d + L->o_status)};
+    return D;
 }
 
-/* Once the chunk's kernels are done (waited for, or with `poll` only if they
- * already are), queues the pack kernel and the D2H of exactly the produced
- * bytes.  Returns 1 when queued, 0 when polling found the kernels running,
- * -1 on an error. */
-static int chunk_collect(struct slot *S, struct layout *L, int poll)
+int pom_decode_lzo_blocks(struct slot *S, const struct layout *L, int concat)
 {
-    if (L->collected)
-        return 1;
+    const struct dev_blocks D = dev_blocks(S, L);
+    const uint32_t n = (uint32_t)L->nlzo;
+    if (concat)
+        return lzo_mi355x_launch_decompress_concat(D.src, D.so, D.sl, D.dst, D.dof, D.dc, D.ol, D.st, n, S->stream);
+    return decompress_dev(D.src, D.so, D.sl, D.dst, D.dof, D.dc, D.ol, D.st, n, S->dmem + L->o_scr, 0, S->stream);
+}
+
+/* ------------------------------------------------------------------------ */
+/* The codec's operations: compress, decompress, decompress_concat          */
+/* ------------------------------------------------------------------------ */
+static size_t compress_cap(const struct hbatch *B, size_t b)
+{
+    return lzo_mi355x_worst_compress(B->src_len[b]);
+}
+
+static size_t decompress_cap(const struct hbatch *B, size_t b)
+{
+    return B->dst_len[b];
+}
+
+static void codec_unreached(const struct hbatch *B, size_t b)
+{
+    B->dst_len[b] = 0;
+}
+
+static void compress_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    (void)nlzo;
+    pom_layout_codec(L, ids, nb, B->src_len, B->cap, lzo_mi355x_compress_scratch((uint32_t)nb));
+}
+
+static void decompress_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    (void)nlzo;
+    pom_layout_codec(L, ids, nb, B->src_len, B->cap, lzo_mi355x_decompress_scratch((uint32_t)nb));
+}
+
+/* The D2H of the lengths and codes, queued behind the kernels. */
+static int codec_lengths_back(struct slot *S, const struct layout *L, int rc)
+{
+    if (rc != 0)
+        return -1;
+    return hipMemcpyAsync(S->hmem + L->u.codec.res_off, S->dmem + L->u.codec.res_off, L->u.codec.res_bytes,
+                          hipMemcpyDeviceToHost, S->stream) == hipSuccess ? 0 : -1;
+}
+
+static int compress_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    /* lzo_mi355x_compress_dev, with the general encoder's pass only when a
+     * block of the chunk needs it: that kernel's workgroups take 64 KB of
+     * LDS each, and behind the other slots' encoders a pass with nothing to
+     * do waited ~0.75 ms for LDS to free up (C5 trace) */
+    const struct dev_blocks D = dev_blocks(S, L);
+    const uint32_t nb = (uint32_t)L->nb;
+    void *scr = nb <= B->enc_lds_max ? NULL : S->dmem + L->o_scr;
+    int big = 0;
+    for (size_t i = 0; i < L->nb; i++)
+        big |= B->src_len[L->ids[i]] > LZO_MI355X_FAST_MAX_N;
+    int rc = lzo_mi355x_launch_compress_fast(D.src, D.so, D.sl, D.dst, D.dof, D.dc, D.ol, D.st, nb, scr,
+                                             scr ? lzo_mi355x_compress_scratch(nb) : 0, S->stream);
+    if (rc == 0 && big)
+        rc = lzo_mi355x_launch_compress(D.src, D.so, D.sl, D.dst, D.dof, D.dc, D.ol, D.st, nb, 1, S->stream);
+    return codec_lengths_back(S, L, rc);
+}
+
+static int decompress_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    (void)B;
+    const int lat = lat_chunk(L, S->hmem, S->dmem, S->stream);
+    return codec_lengths_back(S, L, lat < 0 ? -1 : lat > 0 ? 0 : pom_decode_lzo_blocks(S, L, 0));
+}
+
+static int concat_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    (void)B;
+    return codec_lengths_back(S, L, pom_decode_lzo_blocks(S, L, 1));
+}
+
+/* The lengths are back: the pack kernel and the D2H of exactly the produced bytes. */
+static int codec_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed_out)
+{
+    (void)B;
     uint8_t *d = S->dmem, *h = S->hmem;
     hipStream_t s = S->stream;
-    if (poll) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady)
-            return 0;
-        if (q != hipSuccess)
-            return -1;
-    } else if (hipStreamSynchronize(s) != hipSuccess) {
-        return -1;
-    }
     const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
     const uint32_t *hdc = (const uint32_t *)(h + L->o_dstcap);
-    uint64_t *poff = (uint64_t *)(h + L->o_poff);
+    uint64_t *poff = (uint64_t *)(h + L->u.codec.o_poff);
     size_t packed = 0;
     for (size_t i = 0; i < L->nb; i++) {
         poff[i] = packed;
         packed += ALIGN_UP((size_t)(hol[i] < hdc[i] ? hol[i] : hdc[i]), 16);
     }
     if (packed &&
-        (hipMemcpyAsync(d + L->o_poff, poff, 8 * L->nb, hipMemcpyHostToDevice, s) != hipSuccess ||
+        (hipMemcpyAsync(d + L->u.codec.o_poff, poff, 8 * L->nb, hipMemcpyHostToDevice, s) != hipSuccess ||
          lzo_mi355x_launch_pack(d + L->o_dst, (const uint64_t *)(d + L->o_dstoff),
                                 (const uint32_t *)(d + L->o_outlen),
                                 (const uint32_t *)(d + L->o_dstcap),
-                                (const uint64_t *)(d + L->o_poff), d + L->o_pack,
+                                (const uint64_t *)(d + L->u.codec.o_poff), d + L->u.codec.o_pack,
                                 (uint32_t)L->nb, s) != 0 ||
-         hipMemcpyAsync(h + L->o_dst, d + L->o_pack, packed, hipMemcpyDeviceToHost, s) !=
+         hipMemcpyAsync(h + L->o_dst, d + L->u.codec.o_pack, packed, hipMemcpyDeviceToHost, s) !=
              hipSuccess))
         return -1;
-    L->packed = packed;
-    L->collected = 1;
-    return 1;
+    *packed_out = packed;
+    return 0;
 }
 
-/* Waits for the chunk's produced bytes and hands lengths, codes and bytes to
- * the caller's arrays.  The next chunk (nS/nL, may be NULL) is collected
- * first (its kernels waited for, its D2H queued), so that its copy runs
- * while this one is unpacked.  (Polling it with hipStreamQuery instead never
- * found it done here.) */
-static int chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
-                         struct slot *nS, struct layout *nL)
+/* Lengths, codes and bytes into the caller's arrays. */
+static int codec_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
 {
-    const double t0 = g_timing ? now_ms() : 0;
-    if (chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
-        return -1;
-    if (nS && chunk_collect(nS, nL, 0) < 0)
-        return -1;
-    const double t1 = g_timing ? now_ms() : 0;
     const uint8_t *h = S->hmem;
     const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
     const int32_t *hst = (const int32_t *)(h + L->o_status);
-    const uint64_t *poff = (const uint64_t *)(h + L->o_poff);
+    const uint64_t *poff = (const uint64_t *)(h + L->u.codec.o_poff);
     struct copy_job *jobs = malloc(L->nb * sizeof(*jobs));
     for (size_t i = 0; i < L->nb; i++) {
         const size_t b = L->ids[i];
@@ -896,1018 +818,9 @@ static int chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *
         B->status[b] = hst[i];
     }
     if (jobs) {
-        copy_jobs(jobs, L->nb);
+        pom_copy_jobs(jobs, L->nb);
         free(jobs);
     }
-    if (g_timing)
-        fprintf(stderr, "  deliver n=%zu: wait %.2f (%zu B) unpack %.2f ms\n", L->nb, t1 - t0,
-                L->packed, now_ms() - t1);
-    return 0;
-}
-
-/* ------------------------------------------------------------------------ */
-/* OP_GC_SCAN chunks: decode, walk (itb_scan.hip), counts and ranges back    */
-/* ------------------------------------------------------------------------ */
-/* A chunk's blocks are its LZO records first (the decoders run over that
- * prefix alone), then the records stored uncompressed, which are walked where
- * they are staged.  Staging (host and device alike up to the inputs' end):
- *   [src_off u64][dst_off u64][scan_off u64][first u64, nb + 1][src_len u32][dst_cap u32]
- *   [status i32][out_len u32][live u32][nranges u32][err i32]   <- D2H, one copy
- *   [adepth u8]
- *   [src bytes, 16-B aligned per block]
- *   host:   [the chunk's ranges]                                 <- D2H, sized after the first
- *   device: [decoded payloads][decoder scratch][ranges, room for every ITE the payloads can hold]
- * No decoded byte leaves the device. */
-struct pom_gc_buf {
-    struct pom_gc_buf *next;
-    uint64_t pad;
-    struct pom_gc_range r[];
-};
-
-/* The ranges a payload of n bytes can yield: one per whole ITE. */
-static size_t gc_max_ranges(size_t n)
-{
-    const size_t ites = n > POM_ITB_ITE_OFF ? (n - POM_ITB_ITE_OFF) / POM_ITE_SIZE : 0;
-    return ites < 1024 ? ites : 1024;
-}
-
-/* ids[0, nb): the LZO blocks to the front (any order inside either part).
- * Returns how many there are. */
-static size_t gc_partition(size_t *ids, size_t nb, const uint8_t *is_lzo)
-{
-    size_t lo = 0, hi = nb;
-    while (lo < hi) {
-        if (is_lzo[ids[lo]]) {
-            lo++;
-        } else {
-            const size_t t = ids[lo];
-            ids[lo] = ids[--hi];
-            ids[hi] = t;
-        }
-    }
-    return lo;
-}
-
-static void gc_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo,
-                           const size_t *src_len, const size_t *cap)
-{
-    memset(L, 0, sizeof(*L));
-    L->nb = nb;
-    L->ids = ids;
-    L->nlzo = nlzo;
-    size_t o = 0;
-    L->o_srcoff = o; o += 8 * nb;
-    L->o_dstoff = o; o += 8 * nb;
-    L->o_scanoff = o; o += 8 * nb;
-    L->o_first = o; o += 8 * (nb + 1);
-    L->o_srclen = o; o += 4 * nb;
-    L->o_dstcap = o; o += 4 * nb;
-    L->o_status = o; o += 4 * nb;
-    L->o_outlen = o; o += 4 * nb;
-    L->o_live = o; o += 4 * nb;
-    L->o_nranges = o; o += 4 * nb;
-    L->o_err = o; o += 4 * nb;
-    L->o_adepth = o; o += nb;
-    o = ALIGN_UP(o, 256);
-    L->o_src = o;
-    size_t s = 0, d = 0, r = 0;
-    for (size_t i = 0; i < nb; i++) {
-        s += ALIGN_UP(src_len[ids[i]], 16);
-        if (i < nlzo)
-            d += ALIGN_UP(cap[ids[i]], 16);
-        r += gc_max_ranges(i < nlzo ? cap[ids[i]] : src_len[ids[i]]);
-    }
-    L->rcap = r;
-    o += ALIGN_UP(s, 256);
-    L->o_dst = o;
-    L->o_hrng = o;
-    L->htotal = o + sizeof(struct pom_gc_range) * r;
-    o += ALIGN_UP(d, 256);
-    L->o_scr = o;
-    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
-    L->o_pack = o;
-    L->dtotal = o + sizeof(struct pom_gc_range) * r;
-}
-
-static void gc_layout_fill(const struct layout *L, uint8_t *h, const struct hbatch *B)
-{
-    uint64_t *so = (uint64_t *)(h + L->o_srcoff);
-    uint64_t *dof = (uint64_t *)(h + L->o_dstoff);
-    uint64_t *sco = (uint64_t *)(h + L->o_scanoff);
-    uint32_t *sl = (uint32_t *)(h + L->o_srclen);
-    uint32_t *dc = (uint32_t *)(h + L->o_dstcap);
-    int32_t *st = (int32_t *)(h + L->o_status);
-    uint32_t *ol = (uint32_t *)(h + L->o_outlen);
-    uint8_t *ad = h + L->o_adepth;
-    size_t s = 0, d = 0;
-    struct copy_job *jobs = malloc(L->nb * sizeof(*jobs));
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        const int lzo = i < L->nlzo;
-        so[i] = s;
-        dof[i] = d;
-        sl[i] = (uint32_t)B->src_len[b];
-        dc[i] = lzo ? (uint32_t)B->cap[b] : 0;
-        /* the walk reads the decoders' status and out_len; a stored payload's are set here */
-        sco[i] = lzo ? L->o_dst + d : L->o_src + s;
-        st[i] = 0;
-        ol[i] = lzo ? 0 : (uint32_t)B->src_len[b];
-        ad[i] = B->gc->adepth[b];
-        if (jobs) {
-            jobs[i].dst = h + L->o_src + s;
-            jobs[i].src = B->src[b];
-            jobs[i].len = B->src_len[b];
-        } else if (B->src_len[b]) {
-            memcpy(h + L->o_src + s, B->src[b], B->src_len[b]);
-        }
-        s += ALIGN_UP(B->src_len[b], 16);
-        d += ALIGN_UP((size_t)dc[i], 16);
-    }
-    if (jobs) {
-        copy_jobs(jobs, L->nb);
-        free(jobs);
-    }
-}
-
-/* As chunk_launch: everything queued on the slot's stream, nothing waited for. */
-static int gc_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
-{
-    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
-        return -1;
-    uint8_t *d = S->dmem, *h = S->hmem;
-    hipStream_t s = S->stream;
-    const uint32_t nb = (uint32_t)L->nb;
-    gc_layout_fill(L, h, B);
-    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
-        return -1;
-    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
-    int32_t *st = (int32_t *)(d + L->o_status);
-    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
-                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
-                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
-        lzo_mi355x_launch_gc_scan(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth, nb,
-                                  (uint32_t)B->gc->column, (uint32_t *)(d + L->o_live),
-                                  (uint32_t *)(d + L->o_nranges), (uint64_t *)(d + L->o_first),
-                                  (struct pom_gc_range *)(d + L->o_pack), L->rcap,
-                                  (int32_t *)(d + L->o_err), s) != 0)
-        return -1;
-    return hipMemcpyAsync(h + L->o_status, d + L->o_status, 20 * L->nb, hipMemcpyDeviceToHost, s) ==
-                   hipSuccess ? 0 : -1;
-}
-
-/* As chunk_collect: once the counts are back, the D2H of exactly the chunk's ranges. */
-static int gc_chunk_collect(struct slot *S, struct layout *L, int poll)
-{
-    if (L->collected)
-        return 1;
-    hipStream_t s = S->stream;
-    if (poll) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady)
-            return 0;
-        if (q != hipSuccess)
-            return -1;
-    } else if (hipStreamSynchronize(s) != hipSuccess) {
-        return -1;
-    }
-    const uint32_t *hnr = (const uint32_t *)(S->hmem + L->o_nranges);
-    size_t total = 0;
-    for (size_t i = 0; i < L->nb; i++)
-        total += hnr[i];
-    if (total > L->rcap)
-        return -1;
-    if (total && hipMemcpyAsync(S->hmem + L->o_hrng, S->dmem + L->o_pack, sizeof(struct pom_gc_range) * total,
-                                hipMemcpyDeviceToHost, s) != hipSuccess)
-        return -1;
-    L->packed = sizeof(struct pom_gc_range) * total;
-    L->collected = 1;
-    return 1;
-}
-
-/* As chunk_deliver: the chunk's ranges into a buffer of their own (the chunks
- * reorder the blocks, so the caller places each block's ranges itself). */
-static int gc_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
-                            struct slot *nS, struct layout *nL)
-{
-    if (gc_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
-        return -1;
-    if (nS && gc_chunk_collect(nS, nL, 0) < 0)
-        return -1;
-    struct pom_gc_sink *G = B->gc;
-    const uint8_t *h = S->hmem;
-    const int32_t *hst = (const int32_t *)(h + L->o_status);
-    const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
-    const uint32_t *hlv = (const uint32_t *)(h + L->o_live);
-    const uint32_t *hnr = (const uint32_t *)(h + L->o_nranges);
-    const int32_t *her = (const int32_t *)(h + L->o_err);
-    struct pom_gc_buf *buf = malloc(sizeof(*buf) + L->packed);
-    if (!buf)
-        return -1;
-    memcpy(buf->r, h + L->o_hrng, L->packed);
-    size_t at = 0;
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        G->status[b] = hst[i];
-        G->out_len[b] = hol[i];
-        G->live[b] = hlv[i];
-        G->nranges[b] = hnr[i];
-        G->err[b] = her[i];
-        G->rng[b] = buf->r + at;
-        at += hnr[i];
-    }
-    pthread_mutex_lock(&G->mu);
-    buf->next = G->bufs;
-    G->bufs = buf;
-    pthread_mutex_unlock(&G->mu);
-    return 0;
-}
-
-void pom_gc_sink_free(struct pom_gc_sink *sink)
-{
-    while (sink->bufs) {
-        struct pom_gc_buf *next = sink->bufs->next;
-        free(sink->bufs);
-        sink->bufs = next;
-    }
-}
-
-/* ------------------------------------------------------------------------ */
-/* OP_READDIR chunks: decode, dentry walk (itb_dents.hip), counts and records */
-/* ------------------------------------------------------------------------ */
-/* OP_GC_SCAN's chunks with the dentry walk in the range walk's place: the same
- * partition (LZO records first) and the same fill (gc_layout_fill); dnum takes
- * nranges' place, a bytes word per block is added, and the packed output is
- * bytes.  Staging:
- *   [src_off u64][dst_off u64][scan_off u64][first u64, nb + 1][src_len u32][dst_cap u32]
- *   [status i32][out_len u32][live u32][dnum u32][bytes u32][err i32]   <- D2H, one copy
- *   [adepth u8]
- *   [src bytes, 16-B aligned per block]
- *   host:   [the chunk's records]                                <- D2H, sized after the first
- *   device: [decoded payloads][decoder scratch][records, 272 bytes for every ITE the payloads can hold]
- * No other decoded byte leaves the device. */
-static void rd_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo,
-                           const size_t *src_len, const size_t *cap)
-{
-    memset(L, 0, sizeof(*L));
-    L->nb = nb;
-    L->ids = ids;
-    L->nlzo = nlzo;
-    size_t o = 0;
-    L->o_srcoff = o; o += 8 * nb;
-    L->o_dstoff = o; o += 8 * nb;
-    L->o_scanoff = o; o += 8 * nb;
-    L->o_first = o; o += 8 * (nb + 1);
-    L->o_srclen = o; o += 4 * nb;
-    L->o_dstcap = o; o += 4 * nb;
-    L->o_status = o; o += 4 * nb;
-    L->o_outlen = o; o += 4 * nb;
-    L->o_live = o; o += 4 * nb;
-    L->o_nranges = o; o += 4 * nb;
-    L->o_bytes = o; o += 4 * nb;
-    L->o_err = o; o += 4 * nb;
-    L->o_adepth = o; o += nb;
-    o = ALIGN_UP(o, 256);
-    L->o_src = o;
-    size_t s = 0, d = 0, r = 0;
-    for (size_t i = 0; i < nb; i++) {
-        s += ALIGN_UP(src_len[ids[i]], 16);
-        if (i < nlzo)
-            d += ALIGN_UP(cap[ids[i]], 16);
-        r += gc_max_ranges(i < nlzo ? cap[ids[i]] : src_len[ids[i]]) * (POM_DENT_HDR + POM_ITE_NAME_MAX);
-    }
-    L->rcap = r;
-    o += ALIGN_UP(s, 256);
-    L->o_dst = o;
-    L->o_hrng = o;
-    L->htotal = o + r;
-    o += ALIGN_UP(d, 256);
-    L->o_scr = o;
-    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
-    L->o_pack = o;
-    L->dtotal = o + r;
-}
-
-/* As gc_chunk_launch. */
-static int rd_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
-{
-    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
-        return -1;
-    uint8_t *d = S->dmem, *h = S->hmem;
-    hipStream_t s = S->stream;
-    const uint32_t nb = (uint32_t)L->nb;
-    gc_layout_fill(L, h, B);
-    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
-        return -1;
-    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
-    int32_t *st = (int32_t *)(d + L->o_status);
-    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
-                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
-                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
-        lzo_mi355x_launch_readdir(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth, nb,
-                                  (uint32_t *)(d + L->o_live), (uint32_t *)(d + L->o_nranges),
-                                  (uint32_t *)(d + L->o_bytes), (uint64_t *)(d + L->o_first),
-                                  d + L->o_pack, L->rcap, (int32_t *)(d + L->o_err), s) != 0)
-        return -1;
-    return hipMemcpyAsync(h + L->o_status, d + L->o_status, 24 * L->nb, hipMemcpyDeviceToHost, s) ==
-                   hipSuccess ? 0 : -1;
-}
-
-/* As gc_chunk_collect: once the counts are back, the D2H of exactly the chunk's records. */
-static int rd_chunk_collect(struct slot *S, struct layout *L, int poll)
-{
-    if (L->collected)
-        return 1;
-    hipStream_t s = S->stream;
-    if (poll) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady)
-            return 0;
-        if (q != hipSuccess)
-            return -1;
-    } else if (hipStreamSynchronize(s) != hipSuccess) {
-        return -1;
-    }
-    const uint32_t *hby = (const uint32_t *)(S->hmem + L->o_bytes);
-    size_t total = 0;
-    for (size_t i = 0; i < L->nb; i++)
-        total += hby[i];
-    if (total > L->rcap)
-        return -1;
-    if (total && hipMemcpyAsync(S->hmem + L->o_hrng, S->dmem + L->o_pack, total, hipMemcpyDeviceToHost, s) !=
-                     hipSuccess)
-        return -1;
-    L->packed = total;
-    L->collected = 1;
-    return 1;
-}
-
-/* As gc_chunk_deliver: the chunk's records into a buffer of their own. */
-static int rd_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
-                            struct slot *nS, struct layout *nL)
-{
-    if (rd_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
-        return -1;
-    if (nS && rd_chunk_collect(nS, nL, 0) < 0)
-        return -1;
-    struct pom_gc_sink *G = B->gc;
-    const uint8_t *h = S->hmem;
-    const int32_t *hst = (const int32_t *)(h + L->o_status);
-    const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
-    const uint32_t *hlv = (const uint32_t *)(h + L->o_live);
-    const uint32_t *hdn = (const uint32_t *)(h + L->o_nranges);
-    const uint32_t *hby = (const uint32_t *)(h + L->o_bytes);
-    const int32_t *her = (const int32_t *)(h + L->o_err);
-    struct pom_gc_buf *buf = malloc(sizeof(*buf) + L->packed);
-    if (!buf)
-        return -1;
-    /* a listing is megabytes where the ranges were kilobytes: block by block, over the copy threads */
-    uint8_t *bytes = (uint8_t *)buf->r;
-    struct copy_job *jobs = malloc((L->nb + 1) * sizeof(*jobs));
-    if (!jobs)
-        memcpy(bytes, h + L->o_hrng, L->packed);
-    size_t at = 0;
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        G->status[b] = hst[i];
-        G->out_len[b] = hol[i];
-        G->live[b] = hlv[i];
-        G->nranges[b] = hdn[i];
-        G->bytes[b] = hby[i];
-        G->err[b] = her[i];
-        G->dents[b] = bytes + at;
-        if (jobs) {
-            jobs[i].dst = bytes + at;
-            jobs[i].src = h + L->o_hrng + at;
-            jobs[i].len = hby[i];
-        }
-        at += hby[i];
-    }
-    if (jobs) {
-        copy_jobs(jobs, L->nb);
-        free(jobs);
-    }
-    pthread_mutex_lock(&G->mu);
-    buf->next = G->bufs;
-    G->bufs = buf;
-    pthread_mutex_unlock(&G->mu);
-    return 0;
-}
-
-/* ------------------------------------------------------------------------ */
-/* OP_KVLIST chunks: decode, key walk (itb_keys.hip), counts and records back */
-/* ------------------------------------------------------------------------ */
-/* OP_READDIR's chunks with the key walk in the dentry walk's place: the same
- * partition and fill; a keybytes word per block and the call's needle, staged
- * once per chunk, are added, the emit masks stay on the device unless the
- * caller asked for them, and a count-only call has no records.  Staging:
- *   [src_off u64][dst_off u64][scan_off u64][first u64, nb + 1][src_len u32][dst_cap u32]
- *   [status i32][out_len u32][live u32][dnum u32][bytes u32][keybytes u32][err i32]   <- D2H, one copy
- *   [adepth u8]
- *   [needle, 256 bytes]
- *   [src bytes, 16-B aligned per block]
- *   host:   [masks, 128 bytes per block, when asked for]         <- D2H behind the counts
- *           [the chunk's records, unless count-only]             <- D2H, sized after the first
- *   device: [decoded payloads][decoder scratch][masks][records, 324 bytes for every ITE the payloads can hold]
- * No other decoded byte leaves the device. */
-static void kv_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
-{
-    const size_t *src_len = B->src_len, *cap = B->cap;
-    memset(L, 0, sizeof(*L));
-    L->nb = nb;
-    L->ids = ids;
-    L->nlzo = nlzo;
-    size_t o = 0;
-    L->o_srcoff = o; o += 8 * nb;
-    L->o_dstoff = o; o += 8 * nb;
-    L->o_scanoff = o; o += 8 * nb;
-    L->o_first = o; o += 8 * (nb + 1);
-    L->o_srclen = o; o += 4 * nb;
-    L->o_dstcap = o; o += 4 * nb;
-    L->o_status = o; o += 4 * nb;
-    L->o_outlen = o; o += 4 * nb;
-    L->o_live = o; o += 4 * nb;
-    L->o_nranges = o; o += 4 * nb;
-    L->o_bytes = o; o += 4 * nb;
-    L->o_keybytes = o; o += 4 * nb;
-    L->o_err = o; o += 4 * nb;
-    L->o_adepth = o; o += nb;
-    o = ALIGN_UP(o, 256);
-    L->o_needle = o; o += 256;
-    L->o_src = o;
-    size_t s = 0, d = 0, r = 0;
-    for (size_t i = 0; i < nb; i++) {
-        s += ALIGN_UP(src_len[ids[i]], 16);
-        if (i < nlzo)
-            d += ALIGN_UP(cap[ids[i]], 16);
-        r += gc_max_ranges(i < nlzo ? cap[ids[i]] : src_len[ids[i]]) * (4 + POM_KV_VALUE_MAX);
-    }
-    const size_t masks = ALIGN_UP(8 * POM_KV_MASK_WORDS * nb, 256);
-    L->rcap = r;
-    o += ALIGN_UP(s, 256);
-    L->o_dst = o;
-    L->o_hmask = o;
-    L->o_hrng = o + (B->gc->mask ? masks : 0);
-    L->htotal = L->o_hrng + (B->gc->count_only ? 0 : r);
-    o += ALIGN_UP(d, 256);
-    L->o_scr = o;
-    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
-    L->o_mask = o;
-    o += masks;
-    L->o_pack = o;
-    L->dtotal = o + r;
-}
-
-/* As rd_chunk_launch. */
-static int kv_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
-{
-    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
-        return -1;
-    uint8_t *d = S->dmem, *h = S->hmem;
-    hipStream_t s = S->stream;
-    const uint32_t nb = (uint32_t)L->nb;
-    const struct pom_gc_sink *G = B->gc;
-    gc_layout_fill(L, h, B);
-    memset(h + L->o_needle, 0, 256);
-    if (G->needle_len)
-        memcpy(h + L->o_needle, G->needle, G->needle_len);
-    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
-        return -1;
-    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
-    int32_t *st = (int32_t *)(d + L->o_status);
-    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
-                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
-                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
-        lzo_mi355x_launch_kvlist(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth, nb,
-                                 G->kv_op, d + L->o_needle, G->needle_len,
-                                 (uint32_t *)(d + L->o_live), (uint32_t *)(d + L->o_nranges),
-                                 (uint32_t *)(d + L->o_bytes), (uint32_t *)(d + L->o_keybytes),
-                                 (uint64_t *)(d + L->o_mask), (uint64_t *)(d + L->o_first),
-                                 d + L->o_pack, G->count_only ? 0 : L->rcap, (int32_t *)(d + L->o_err), s) != 0)
-        return -1;
-    if (hipMemcpyAsync(h + L->o_status, d + L->o_status, 28 * L->nb, hipMemcpyDeviceToHost, s) != hipSuccess)
-        return -1;
-    if (G->mask && hipMemcpyAsync(h + L->o_hmask, d + L->o_mask, 8 * POM_KV_MASK_WORDS * L->nb,
-                                  hipMemcpyDeviceToHost, s) != hipSuccess)
-        return -1;
-    return 0;
-}
-
-/* As rd_chunk_collect; a count-only chunk has nothing more to fetch. */
-static int kv_chunk_collect(struct slot *S, struct layout *L, const struct hbatch *B, int poll)
-{
-    if (L->collected)
-        return 1;
-    hipStream_t s = S->stream;
-    if (poll) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady)
-            return 0;
-        if (q != hipSuccess)
-            return -1;
-    } else if (hipStreamSynchronize(s) != hipSuccess) {
-        return -1;
-    }
-    size_t total = 0;
-    if (!B->gc->count_only) {
-        const uint32_t *hby = (const uint32_t *)(S->hmem + L->o_bytes);
-        for (size_t i = 0; i < L->nb; i++)
-            total += hby[i];
-        if (total > L->rcap)
-            return -1;
-        if (total && hipMemcpyAsync(S->hmem + L->o_hrng, S->dmem + L->o_pack, total, hipMemcpyDeviceToHost, s) !=
-                         hipSuccess)
-            return -1;
-    }
-    L->packed = total;
-    L->collected = 1;
-    return 1;
-}
-
-/* As rd_chunk_deliver. */
-static int kv_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
-                            struct slot *nS, struct layout *nL)
-{
-    if (kv_chunk_collect(S, L, B, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
-        return -1;
-    if (nS && kv_chunk_collect(nS, nL, B, 0) < 0)
-        return -1;
-    struct pom_gc_sink *G = B->gc;
-    const uint8_t *h = S->hmem;
-    const int32_t *hst = (const int32_t *)(h + L->o_status);
-    const uint32_t *hol = (const uint32_t *)(h + L->o_outlen);
-    const uint32_t *hlv = (const uint32_t *)(h + L->o_live);
-    const uint32_t *hdn = (const uint32_t *)(h + L->o_nranges);
-    const uint32_t *hby = (const uint32_t *)(h + L->o_bytes);
-    const uint32_t *hkb = (const uint32_t *)(h + L->o_keybytes);
-    const int32_t *her = (const int32_t *)(h + L->o_err);
-    struct pom_gc_buf *buf = malloc(sizeof(*buf) + L->packed);
-    if (!buf)
-        return -1;
-    uint8_t *bytes = (uint8_t *)buf->r;
-    struct copy_job *jobs = malloc((L->nb + 1) * sizeof(*jobs));
-    if (!jobs)
-        memcpy(bytes, h + L->o_hrng, L->packed);
-    size_t at = 0;
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        const size_t nbytes = G->count_only ? 0 : hby[i];
-        G->status[b] = hst[i];
-        G->out_len[b] = hol[i];
-        G->live[b] = hlv[i];
-        G->nranges[b] = hdn[i];
-        G->bytes[b] = hby[i];
-        G->keybytes[b] = hkb[i];
-        G->err[b] = her[i];
-        G->dents[b] = G->count_only ? NULL : bytes + at;
-        if (G->mask)
-            memcpy(G->mask + POM_KV_MASK_WORDS * b, h + L->o_hmask + 8 * POM_KV_MASK_WORDS * i, 8 * POM_KV_MASK_WORDS);
-        if (jobs) {
-            jobs[i].dst = bytes + at;
-            jobs[i].src = h + L->o_hrng + at;
-            jobs[i].len = nbytes;
-        }
-        at += nbytes;
-    }
-    if (jobs) {
-        copy_jobs(jobs, L->nb);
-        free(jobs);
-    }
-    pthread_mutex_lock(&G->mu);
-    buf->next = G->bufs;
-    G->bufs = buf;
-    pthread_mutex_unlock(&G->mu);
-    return 0;
-}
-
-/* ------------------------------------------------------------------------ */
-/* OP_COL_READ chunks: decode, region copy (col_slice.hip), slices back       */
-/* ------------------------------------------------------------------------ */
-/* A column and all its requests are in one chunk; request j of the chunk is
- * the j-th in block order, then in the block's own order.  The recorded
- * length, the offset and the size are all known here, so every request's
- * clamped length and its 16-byte-aligned place among the chunk's slices are
- * known before the launch: one copy of a known size brings back codes and
- * slices, with no sizing round trip between two copies (the bytes of a request
- * that ends in an error are copied and ignored).  That copy is queued once the
- * chunk's kernels are done, as chunk_collect queues its own.  Queued with the
- * launch, the chunks' decodes ran one after another instead of side by side
- * (64 columns of 4 MiB, 32 reads each: 83 ms a call against 36 ms; DESIGN
- * 5.7) -- as if the copy, waiting for its chunk's decode, held up the next
- * chunks' copies to the device, and with them their kernels.  Staging (host and
- * device alike up to the inputs' end):
- *   [src_off u64][dst_off u64][want u64][out_off u64, nreq][requests, nreq][src_len u32][dst_cap u32]
- *   [src bytes, 16-B aligned per block]
- *   device: [decoded columns, 16-B aligned][decoder scratch]
- *   both:   [status i32][out_len u32][slice len u32, nreq][slice err i32, nreq][slices]  <- D2H, one copy
- * No other decoded byte leaves the device. */
-static size_t cr_slot(const struct pom_col_sink *C, size_t b, size_t k)
-{
-    const struct pom_col_req *q = &C->req[C->req_ids[k]];
-    const uint64_t w = C->want[b];
-    const uint64_t n = q->offset > w ? 0 : q->size < w - q->offset ? q->size : w - q->offset;
-    return ALIGN_UP((size_t)n, 16);
-}
-
-static void cr_layout_make(struct layout *L, const size_t *ids, size_t nb, const struct hbatch *B)
-{
-    const struct pom_col_sink *C = B->cr;
-    memset(L, 0, sizeof(*L));
-    L->nb = nb;
-    L->ids = ids;
-    size_t s = 0, d = 0, nr = 0, sl = 0;
-    for (size_t i = 0; i < nb; i++) {
-        const size_t b = ids[i];
-        s += ALIGN_UP(B->src_len[b], 16);
-        d += ALIGN_UP(B->cap[b], 16);
-        for (size_t k = C->req_first[b]; k < C->req_first[b + 1]; k++, nr++)
-            sl += cr_slot(C, b, k);
-    }
-    L->nreq = nr;
-    size_t o = 0;
-    L->o_srcoff = o; o += 8 * nb;
-    L->o_dstoff = o; o += 8 * nb;
-    L->o_want = o; o += 8 * nb;
-    L->o_outoff = o; o += 8 * nr;
-    L->o_req = o; o += sizeof(struct pom_col_req) * nr;
-    L->o_srclen = o; o += 4 * nb;
-    L->o_dstcap = o; o += 4 * nb;
-    o = ALIGN_UP(o, 256);
-    L->o_src = o;
-    o += ALIGN_UP(s, 256);
-    L->o_dst = o;
-    L->res_hdr = ALIGN_UP(8 * nb + 8 * nr, 16);
-    L->res_bytes = L->res_hdr + sl;
-    L->o_hres = o;
-    L->htotal = o + L->res_bytes;
-    o += ALIGN_UP(d, 256);
-    L->o_scr = o;
-    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nb), 256);
-    L->o_res = o;
-    L->o_status = o;
-    L->o_outlen = o + 4 * nb;
-    L->dtotal = o + L->res_bytes;
-}
-
-static void cr_layout_fill(const struct layout *L, uint8_t *h, const struct hbatch *B)
-{
-    const struct pom_col_sink *C = B->cr;
-    uint64_t *so = (uint64_t *)(h + L->o_srcoff);
-    uint64_t *dof = (uint64_t *)(h + L->o_dstoff);
-    uint64_t *wt = (uint64_t *)(h + L->o_want);
-    uint64_t *oo = (uint64_t *)(h + L->o_outoff);
-    struct pom_col_req *rq = (struct pom_col_req *)(h + L->o_req);
-    uint32_t *sl = (uint32_t *)(h + L->o_srclen);
-    uint32_t *dc = (uint32_t *)(h + L->o_dstcap);
-    size_t s = 0, d = 0, j = 0, at = 0;
-    struct copy_job *jobs = malloc(L->nb * sizeof(*jobs));
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        so[i] = s;
-        dof[i] = d;
-        wt[i] = C->want[b];
-        sl[i] = (uint32_t)B->src_len[b];
-        dc[i] = (uint32_t)B->cap[b];
-        for (size_t k = C->req_first[b]; k < C->req_first[b + 1]; k++, j++) {
-            const struct pom_col_req *q = &C->req[C->req_ids[k]];
-            rq[j].offset = q->offset;
-            rq[j].size = q->size;
-            rq[j].col = (uint32_t)i;            /* the chunk's own column index */
-            rq[j].pad = 0;
-            oo[j] = at;
-            at += cr_slot(C, b, k);
-        }
-        if (jobs) {
-            jobs[i].dst = h + L->o_src + s;
-            jobs[i].src = B->src[b];
-            jobs[i].len = B->src_len[b];
-        } else if (B->src_len[b]) {
-            memcpy(h + L->o_src + s, B->src[b], B->src_len[b]);
-        }
-        s += ALIGN_UP(B->src_len[b], 16);
-        d += ALIGN_UP(B->cap[b], 16);
-    }
-    if (jobs) {
-        copy_jobs(jobs, L->nb);
-        free(jobs);
-    }
-}
-
-/* As chunk_launch: everything queued on the slot's stream, nothing waited for. */
-static int cr_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
-{
-    if (L->nreq > 0xFFFFFFFFu || slot_reserve(S, L->dtotal, L->htotal) != 0)
-        return -1;
-    uint8_t *d = S->dmem, *h = S->hmem;
-    hipStream_t s = S->stream;
-    const uint32_t nb = (uint32_t)L->nb;
-    const double t0 = g_timing ? now_ms() : 0;
-    cr_layout_fill(L, h, B);
-    if (g_timing)
-        fprintf(stderr, "  chunk n=%u, %zu requests: fill %.2f ms (%zu B)\n", nb, L->nreq, now_ms() - t0, L->htotal);
-    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
-        return -1;
-    const uint64_t *so = (const uint64_t *)(d + L->o_srcoff);
-    const uint64_t *dof = (const uint64_t *)(d + L->o_dstoff);
-    const uint32_t *sl = (const uint32_t *)(d + L->o_srclen);
-    const uint32_t *dc = (const uint32_t *)(d + L->o_dstcap);
-    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
-    int32_t *st = (int32_t *)(d + L->o_status);
-    uint32_t *rl = (uint32_t *)(d + L->o_res + 8 * L->nb);
-    int32_t *re = (int32_t *)(d + L->o_res + 8 * L->nb + 4 * L->nreq);
-    const int rc = B->cr->concat
-        ? lzo_mi355x_launch_decompress_concat(d + L->o_src, so, sl, d + L->o_dst, dof, dc, ol, st, nb, s)
-        : decompress_dev(d + L->o_src, so, sl, d + L->o_dst, dof, dc, ol, st, nb, d + L->o_scr, 0, s);
-    if (rc != 0 ||
-        lzo_mi355x_launch_col_slice(d + L->o_dst, dof, ol, st, (const uint64_t *)(d + L->o_want), nb,
-                                    (const struct pom_col_req *)(d + L->o_req), (uint32_t)L->nreq,
-                                    d + L->o_res + L->res_hdr, (const uint64_t *)(d + L->o_outoff), rl, re,
-                                    s) != 0)
-        return -1;
-    return 0;
-}
-
-/* As chunk_collect: once the chunk's kernels are done, the one D2H of codes and slices. */
-static int cr_chunk_collect(struct slot *S, struct layout *L, int poll)
-{
-    if (L->collected)
-        return 1;
-    hipStream_t s = S->stream;
-    if (poll) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady)
-            return 0;
-        if (q != hipSuccess)
-            return -1;
-    } else if (hipStreamSynchronize(s) != hipSuccess) {
-        return -1;
-    }
-    if (hipMemcpyAsync(S->hmem + L->o_hres, S->dmem + L->o_res, L->res_bytes, hipMemcpyDeviceToHost, s) !=
-        hipSuccess)
-        return -1;
-    L->packed = L->res_bytes;
-    L->collected = 1;
-    return 1;
-}
-
-/* As chunk_deliver: the next chunk's copy runs while this one is unpacked. */
-static int cr_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
-                            struct slot *nS, struct layout *nL)
-{
-    const double t0 = g_timing ? now_ms() : 0;
-    if (cr_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
-        return -1;
-    if (nS && cr_chunk_collect(nS, nL, 0) < 0)
-        return -1;
-    const double t1 = g_timing ? now_ms() : 0;
-    struct pom_col_sink *C = B->cr;
-    const uint8_t *res = S->hmem + L->o_hres;
-    const uint64_t *oo = (const uint64_t *)(S->hmem + L->o_outoff);
-    const int32_t *hst = (const int32_t *)res;
-    const uint32_t *hrl = (const uint32_t *)(res + 8 * L->nb);
-    const int32_t *hre = (const int32_t *)(res + 8 * L->nb + 4 * L->nreq);
-    struct copy_job *jobs = malloc((L->nreq + 1) * sizeof(*jobs));
-    size_t j = 0;
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        C->status[b] = hst[i];
-        for (size_t k = C->req_first[b]; k < C->req_first[b + 1]; k++, j++) {
-            const size_t r = C->req_ids[k];
-            const size_t n = hre[j] == 0 ? hrl[j] : 0;
-            C->err[r] = hre[j];
-            C->out_len[r] = n;
-            if (jobs) {
-                jobs[j].dst = C->out[r];
-                jobs[j].src = res + L->res_hdr + oo[j];
-                jobs[j].len = n;
-            } else if (n) {
-                memcpy(C->out[r], res + L->res_hdr + oo[j], n);
-            }
-        }
-    }
-    if (jobs) {
-        copy_jobs(jobs, L->nreq);
-        free(jobs);
-    }
-    if (g_timing)
-        fprintf(stderr, "  deliver n=%zu: wait %.2f (%zu B) unpack %.2f ms\n", L->nb, t1 - t0, L->packed,
-                now_ms() - t1);
-    return 0;
-}
-
-/* ------------------------------------------------------------------------ */
-/* OP_LOOKUP chunks: decode, chain walk (itb_find.hip), matched MDUs back     */
-/* ------------------------------------------------------------------------ */
-/* OP_GC_SCAN's partition (LZO records first, stored ones walked as staged)
- * with OP_COL_READ's requests: an ITB and all its requests are in one chunk;
- * request j of the chunk is the j-th in block order, then in the block's own
- * order, renumbered to the chunk's ITB index, its name staged in a blob of the
- * chunk's own.  A request whose name the caller's blob does not hold, or whose
- * namelen is above 255, gets no name bytes and a name_off past the chunk's
- * blob: the kernel's rule 4 refuses it, behind rules 1 to 3 as everywhere.
- * Every result has a fixed size, so one copy of a known size brings them back,
- * queued once the chunk's kernels are done (cr_chunk_collect says why).  The
- * decoder's status reaches the host through the requests' err.  Staging (host
- * and device alike up to the inputs' end):
- *   [src_off u64][dst_off u64][scan_off u64][requests, nreq][src_len u32][dst_cap u32]
- *   [status i32][out_len u32][adepth u8]
- *   [src bytes, 16-B aligned per block][names]
- *   device: [decoded payloads][decoder scratch]
- *   both:   [err i32, nreq][nr u32, nreq][depth u32, nreq][records, 136 * nreq]  <- D2H, one copy
- * No other decoded byte leaves the device. */
-static int lk_name_ok(const struct pom_lookup_sink *K, const struct pom_lookup_req *q)
-{
-    return q->namelen <= 255 && (size_t)q->name_off + q->namelen <= K->names_len;
-}
-
-static size_t lk_name_bytes(const struct pom_lookup_sink *K, const struct pom_lookup_req *q)
-{
-    return lk_name_ok(K, q) ? q->namelen : 0;
-}
-
-static void lk_layout_make(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
-{
-    const struct pom_lookup_sink *K = B->lk;
-    memset(L, 0, sizeof(*L));
-    L->nb = nb;
-    L->ids = ids;
-    L->nlzo = nlzo;
-    size_t s = 0, d = 0, nr = 0, nm = 0;
-    for (size_t i = 0; i < nb; i++) {
-        const size_t b = ids[i];
-        s += ALIGN_UP(B->src_len[b], 16);
-        if (i < nlzo)
-            d += ALIGN_UP(B->cap[b], 16);
-        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, nr++)
-            nm += lk_name_bytes(K, &K->req[K->req_ids[k]]);
-    }
-    L->nreq = nr;
-    L->names_bytes = nm;
-    size_t o = 0;
-    L->o_srcoff = o; o += 8 * nb;
-    L->o_dstoff = o; o += 8 * nb;
-    L->o_scanoff = o; o += 8 * nb;
-    L->o_req = o; o += sizeof(struct pom_lookup_req) * nr;
-    L->o_srclen = o; o += 4 * nb;
-    L->o_dstcap = o; o += 4 * nb;
-    L->o_status = o; o += 4 * nb;
-    L->o_outlen = o; o += 4 * nb;
-    L->o_adepth = o; o += nb;
-    o = ALIGN_UP(o, 256);
-    L->o_src = o;
-    o += ALIGN_UP(s, 256);
-    L->o_names = o;
-    o += ALIGN_UP(nm, 256);
-    L->o_dst = o;
-    L->res_hdr = ALIGN_UP(12 * nr, 16);
-    L->res_bytes = L->res_hdr + POM_LK_REC_SIZE * nr;
-    L->o_hres = o;
-    L->htotal = o + L->res_bytes;
-    o += ALIGN_UP(d, 256);
-    L->o_scr = o;
-    o += ALIGN_UP(lzo_mi355x_decompress_scratch((uint32_t)nlzo), 256);
-    L->o_res = o;
-    L->dtotal = o + L->res_bytes;
-}
-
-static void lk_layout_fill(const struct layout *L, uint8_t *h, const struct hbatch *B)
-{
-    const struct pom_lookup_sink *K = B->lk;
-    uint64_t *so = (uint64_t *)(h + L->o_srcoff);
-    uint64_t *dof = (uint64_t *)(h + L->o_dstoff);
-    uint64_t *sco = (uint64_t *)(h + L->o_scanoff);
-    struct pom_lookup_req *rq = (struct pom_lookup_req *)(h + L->o_req);
-    uint32_t *sl = (uint32_t *)(h + L->o_srclen);
-    uint32_t *dc = (uint32_t *)(h + L->o_dstcap);
-    int32_t *st = (int32_t *)(h + L->o_status);
-    uint32_t *ol = (uint32_t *)(h + L->o_outlen);
-    uint8_t *ad = h + L->o_adepth;
-    uint8_t *nm = h + L->o_names;
-    size_t s = 0, d = 0, j = 0, at = 0;
-    struct copy_job *jobs = malloc(L->nb * sizeof(*jobs));
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        const int lzo = i < L->nlzo;
-        so[i] = s;
-        dof[i] = d;
-        sl[i] = (uint32_t)B->src_len[b];
-        dc[i] = lzo ? (uint32_t)B->cap[b] : 0;
-        /* the walk reads the decoders' status and out_len; a stored payload's are set here */
-        sco[i] = lzo ? L->o_dst + d : L->o_src + s;
-        st[i] = 0;
-        ol[i] = lzo ? 0 : (uint32_t)B->src_len[b];
-        ad[i] = K->adepth[b];
-        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
-            const struct pom_lookup_req *q = &K->req[K->req_ids[k]];
-            const size_t n = lk_name_bytes(K, q);
-            rq[j] = *q;
-            rq[j].itb = (uint32_t)i;            /* the chunk's own ITB index */
-            if (lk_name_ok(K, q)) {
-                rq[j].name_off = (uint32_t)at;
-                if (n)
-                    memcpy(nm + at, K->names + q->name_off, n);
-                at += n;
-            } else {
-                rq[j].name_off = 0xFFFFFFFFu;   /* outside the chunk's blob, as it was outside the caller's */
-            }
-        }
-        if (jobs) {
-            jobs[i].dst = h + L->o_src + s;
-            jobs[i].src = B->src[b];
-            jobs[i].len = B->src_len[b];
-        } else if (B->src_len[b]) {
-            memcpy(h + L->o_src + s, B->src[b], B->src_len[b]);
-        }
-        s += ALIGN_UP(B->src_len[b], 16);
-        d += ALIGN_UP((size_t)dc[i], 16);
-    }
-    if (jobs) {
-        copy_jobs(jobs, L->nb);
-        free(jobs);
-    }
-}
-
-/* As gc_chunk_launch: everything queued on the slot's stream, nothing waited for. */
-static int lk_chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
-{
-    if (L->nreq > 0xFFFFFFFFu || L->names_bytes > 0xFFFFFFF0u || slot_reserve(S, L->dtotal, L->htotal) != 0)
-        return -1;
-    uint8_t *d = S->dmem, *h = S->hmem;
-    hipStream_t s = S->stream;
-    const double t0 = g_timing ? now_ms() : 0;
-    lk_layout_fill(L, h, B);
-    if (g_timing)
-        fprintf(stderr, "  chunk n=%zu, %zu requests: fill %.2f ms (%zu B)\n", L->nb, L->nreq, now_ms() - t0, L->htotal);
-    if (hipMemcpyAsync(d, h, L->o_dst, hipMemcpyHostToDevice, s) != hipSuccess)
-        return -1;
-    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
-    int32_t *st = (int32_t *)(d + L->o_status);
-    uint8_t *res = d + L->o_res;
-    if (decompress_dev(d + L->o_src, (const uint64_t *)(d + L->o_srcoff), (const uint32_t *)(d + L->o_srclen),
-                       d + L->o_dst, (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
-                       ol, st, (uint32_t)L->nlzo, d + L->o_scr, 0, s) != 0 ||
-        lzo_mi355x_launch_lookup(d, (const uint64_t *)(d + L->o_scanoff), ol, st, d + L->o_adepth,
-                                 (uint32_t)L->nb, (const struct pom_lookup_req *)(d + L->o_req),
-                                 (uint32_t)L->nreq, d + L->o_names, (uint32_t)L->names_bytes, (int32_t *)res,
-                                 (uint32_t *)(res + 4 * L->nreq), (uint32_t *)(res + 8 * L->nreq),
-                                 res + L->res_hdr, s) != 0)
-        return -1;
-    return 0;
-}
-
-/* As cr_chunk_collect: once the chunk's kernels are done, the one D2H of codes and records. */
-static int lk_chunk_collect(struct slot *S, struct layout *L, int poll)
-{
-    if (L->collected)
-        return 1;
-    hipStream_t s = S->stream;
-    if (poll) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady)
-            return 0;
-        if (q != hipSuccess)
-            return -1;
-    } else if (hipStreamSynchronize(s) != hipSuccess) {
-        return -1;
-    }
-    if (L->res_bytes && hipMemcpyAsync(S->hmem + L->o_hres, S->dmem + L->o_res, L->res_bytes,
-                                       hipMemcpyDeviceToHost, s) != hipSuccess)
-        return -1;
-    L->packed = L->res_bytes;
-    L->collected = 1;
-    return 1;
-}
-
-/* As cr_chunk_deliver: the results go to their places in the caller's request order. */
-static int lk_chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
-                            struct slot *nS, struct layout *nL)
-{
-    const double t0 = g_timing ? now_ms() : 0;
-    if (lk_chunk_collect(S, L, 0) < 0 || hipStreamSynchronize(S->stream) != hipSuccess)
-        return -1;
-    if (nS && lk_chunk_collect(nS, nL, 0) < 0)
-        return -1;
-    const double t1 = g_timing ? now_ms() : 0;
-    struct pom_lookup_sink *K = B->lk;
-    const uint8_t *res = S->hmem + L->o_hres;
-    const int32_t *he = (const int32_t *)res;
-    const uint32_t *hn = (const uint32_t *)(res + 4 * L->nreq);
-    const uint32_t *hd = (const uint32_t *)(res + 8 * L->nreq);
-    const uint8_t *recs = res + L->res_hdr;
-    size_t j = 0;
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        K->status[b] = 0;                       /* delivered; the decoder's code is in the requests' err */
-        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
-            const size_t r = K->req_ids[k];
-            K->err[r] = he[j];
-            K->nr[r] = hn[j];
-            K->depth[r] = hd[j];
-            memcpy(K->out + POM_LK_REC_SIZE * r, recs + POM_LK_REC_SIZE * j, POM_LK_REC_SIZE);
-        }
-    }
-    if (g_timing)
-        fprintf(stderr, "  deliver n=%zu: wait %.2f (%zu B) unpack %.2f ms\n", L->nb, t1 - t0, L->packed,
-                now_ms() - t1);
     return 0;
 }
 
@@ -1932,6 +845,83 @@ static const size_t kChunkBudgetCompress = (size_t)128 << 20;
 static const size_t kChunkBlocks = (size_t)1 << 20;
 /* below this many bytes per device a batch stays on one device */
 static const size_t kSplitMinBytes = (size_t)64 << 20;
+
+static const struct chunk_ops compress_ops = {
+    "compress", 1, compress_cap, NULL, codec_unreached, compress_layout,
+    pom_stage_inputs, compress_kernels, codec_collect, codec_unpack};
+static const struct chunk_ops decompress_ops = {
+    "decompress", 0, decompress_cap, NULL, codec_unreached, decompress_layout,
+    pom_stage_inputs, decompress_kernels, codec_collect, codec_unpack};
+static const struct chunk_ops concat_ops = {
+    "decompress", 0, decompress_cap, NULL, codec_unreached, decompress_layout,
+    pom_stage_inputs, concat_kernels, codec_collect, codec_unpack};
+
+/* Chunk on slot S: inputs into pinned staging, H2D, kernels, D2H of what needs
+ * no sizing -- all queued on the slot's stream, nothing waited for. */
+static int chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
+{
+    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
+        return -1;
+    const double t0 = g_timing ? now_ms() : 0;
+    if (B->ops->stage(L, S->hmem, B) != 0)
+        return -1;
+    if (g_timing)
+        fprintf(stderr, "  chunk n=%zu: fill %.2f ms (%zu B)\n", L->nb, now_ms() - t0, L->htotal);
+    if (hipMemcpyAsync(S->dmem, S->hmem, L->o_dst, hipMemcpyHostToDevice, S->stream) != hipSuccess)
+        return -1;
+    return B->ops->kernels(S, L, B);
+}
+
+/* Waits for the chunk's kernels, then queues the D2H that needed their
+ * results (codec chunks: the pack kernel and exactly the produced bytes).
+ * Once per chunk: the delivery of the chunk before may have done it already. */
+static int chunk_collect(struct slot *S, struct layout *L, const struct hbatch *B)
+{
+    if (L->collected)
+        return 0;
+    if (hipStreamSynchronize(S->stream) != hipSuccess || B->ops->collect(S, L, B, &L->packed) != 0)
+        return -1;
+    L->collected = 1;
+    return 0;
+}
+
+/* Waits for the chunk's results and hands them to the caller's arrays or
+ * sink.  The next chunk (nS/nL, may be NULL) is collected first (its kernels
+ * waited for, its D2H queued), so that its copy runs while this one is
+ * unpacked.  (Polling it with hipStreamQuery instead never found it done
+ * here.) */
+static int chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
+                         struct slot *nS, struct layout *nL)
+{
+    const double t0 = g_timing ? now_ms() : 0;
+    if (chunk_collect(S, L, B) != 0 || hipStreamSynchronize(S->stream) != hipSuccess)
+        return -1;
+    if (nS && chunk_collect(nS, nL, B) != 0)
+        return -1;
+    const double t1 = g_timing ? now_ms() : 0;
+    const int rc = B->ops->unpack(S, L, B);
+    if (g_timing)
+        fprintf(stderr, "  deliver n=%zu: wait %.2f (%zu B) unpack %.2f ms\n", L->nb, t1 - t0,
+                L->packed, now_ms() - t1);
+    return rc;
+}
+
+/* ids[0, nb): the LZO blocks to the front (any order inside either part).
+ * Returns how many there are. */
+static size_t lzo_blocks_first(size_t *ids, size_t nb, const uint8_t *is_lzo)
+{
+    size_t lo = 0, hi = nb;
+    while (lo < hi) {
+        if (is_lzo[ids[lo]]) {
+            lo++;
+        } else {
+            const size_t t = ids[lo];
+            ids[lo] = ids[--hi];
+            ids[hi] = t;
+        }
+    }
+    return lo;
+}
 
 /* Completion order (compress batches, hbatch.ooo): the first live slot whose
  * stream is done, polling every 20 us; a failed stream counts as done (its
@@ -1969,19 +959,13 @@ static int dev_run(void *arg, int d)
          * back while the chunks of the largest blocks decode (debug key
          * dec_small_first=0: largest first, as compress batches) */
         size_t *rev = NULL;
-        if (B->kind != OP_COMPRESS && nids > 1 && pom_dbg_int("dec_small_first", 1) != 0 &&
-            (rev = malloc(nids * sizeof(*rev))) != NULL) {
+        if (B->small_first && nids > 1 && (rev = malloc(nids * sizeof(*rev))) != NULL) {
             for (size_t i = 0; i < nids; i++)
                 rev[i] = ids[nids - 1 - i];
             ids = rev;
         }
-        /* walk chunks put their LZO blocks first (gc_partition): in a copy of the ids */
-        const int gc = B->kind == OP_GC_SCAN;
-        const int cr = B->kind == OP_COL_READ;
-        const int rd = B->kind == OP_READDIR;
-        const int lk = B->kind == OP_LOOKUP;
-        const int kv = B->kind == OP_KVLIST;
-        if ((gc || rd || lk || kv) && !rev) {
+        /* chunks with stored blocks put their LZO blocks first (lzo_blocks_first): in a copy of the ids */
+        if (B->is_lzo && !rev) {
             if ((rev = malloc(nids * sizeof(*rev))) != NULL) {
                 memcpy(rev, ids, nids * sizeof(*rev));
                 ids = rev;
@@ -2022,9 +1006,7 @@ static int dev_run(void *arg, int d)
             if (dj >= 0) {
                 const int ahead = !B->ooo && live[nxt] && nxt != dj;
                 const int fail = fail_at >= 0 && ndeliv++ == fail_at;
-                if (fail || (gc ? gc_chunk_deliver : cr ? cr_chunk_deliver : rd ? rd_chunk_deliver
-                                : lk ? lk_chunk_deliver : kv ? kv_chunk_deliver : chunk_deliver)(
-                                &c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL, &L[nxt]) != 0) {
+                if (fail || chunk_deliver(&c->s[dj], &L[dj], B, ahead ? &c->s[nxt] : NULL, &L[nxt]) != 0) {
                     rc = -1;
                     for (int j = 0; j < B->nslots; j++)
                         hipStreamSynchronize(c->s[j].stream);
@@ -2040,30 +1022,14 @@ static int dev_run(void *arg, int d)
             if (more) {
                 const size_t end = pom_chunk_end(ids, from, nids, B->cost,
                                                  k ? B->budget : B->budget / 4, kChunkBlocks);
-                if (gc)
-                    gc_layout_make(&L[cur], ids + from, end - from,
-                                   gc_partition(rev + from, end - from, B->gc->is_lzo), B->src_len, B->cap);
-                else if (cr)
-                    cr_layout_make(&L[cur], ids + from, end - from, B);
-                else if (rd)
-                    rd_layout_make(&L[cur], ids + from, end - from,
-                                   gc_partition(rev + from, end - from, B->gc->is_lzo), B->src_len, B->cap);
-                else if (lk)
-                    lk_layout_make(&L[cur], ids + from, end - from,
-                                   gc_partition(rev + from, end - from, B->lk->is_lzo), B);
-                else if (kv)
-                    kv_layout_make(&L[cur], ids + from, end - from,
-                                   gc_partition(rev + from, end - from, B->gc->is_lzo), B);
-                else
-                    layout_make(&L[cur], ids + from, end - from, B->src_len, B->cap,
-                                B->kind == OP_COMPRESS);
+                const size_t nb = end - from;
+                B->ops->layout(&L[cur], ids + from, nb,
+                               B->is_lzo ? lzo_blocks_first(rev + from, nb, B->is_lzo) : nb, B);
                 /* the caller may produce the chunk's inputs now (e.g. read them),
                  * while the chunks in flight are copied and decoded */
                 if (B->pre_chunk)
-                    B->pre_chunk(B->cb_ctx, ids + from, end - from);
-                if ((gc ? gc_chunk_launch : cr ? cr_chunk_launch : rd ? rd_chunk_launch
-                        : lk ? lk_chunk_launch : kv ? kv_chunk_launch : chunk_launch)(
-                        &c->s[cur], &L[cur], B) != 0) {
+                    B->pre_chunk(B->cb_ctx, ids + from, nb);
+                if (chunk_launch(&c->s[cur], &L[cur], B) != 0) {
                     rc = -1;
                     hipStreamSynchronize(c->s[cur].stream);
                 } else {
@@ -2120,47 +1086,12 @@ static int batch_devices(int *devs)
     return n;
 }
 
-static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
-                           uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
-                           pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
-                           struct pom_gc_sink *gc, struct pom_col_sink *cr, struct pom_lookup_sink *lk);
-
-static int batch_common(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
-                        uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks)
+int pom_host_batch(struct hbatch *B, size_t nblocks)
 {
-    return batch_common_cb(kind, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL, NULL, NULL, NULL);
-}
-
-/* lzo_mi355x_decompress_batch with pre_chunk(ctx, ids, nb) called before each
- * chunk's inputs are staged: the caller fills src[ids[i]] (src_len is known
- * up front) while earlier chunks are on the GPU.  Same threads as
- * pom_compress_batch_chunked. */
-int pom_decompress_batch_chunked(const uint8_t *const *src, const size_t *src_len, uint8_t *const *dst,
-                                 size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn pre_chunk,
-                                 void *ctx)
-{
-    return batch_common_cb(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx, NULL, NULL, NULL);
-}
-
-/* lzo_mi355x_compress_batch with on_chunk(ctx, ids, nb) called as each chunk's
- * blocks (ids into the caller's arrays) are delivered -- from the thread
- * running that device's chunks, so concurrently for batches split over
- * several GPUs. */
-int pom_compress_batch_chunked(const uint8_t *const *src, const size_t *src_len, uint8_t *const *dst,
-                               size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn on_chunk,
-                               void *ctx)
-{
-    return batch_common_cb(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx, NULL, NULL, NULL);
-}
-
-static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const size_t *src_len,
-                           uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
-                           pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx,
-                           struct pom_gc_sink *gc, struct pom_col_sink *cr, struct pom_lookup_sink *lk)
-{
+    const struct chunk_ops *ops = B->ops;
     const double t0 = g_timing ? now_ms() : 0;
-    struct tctx *t = tctx_get();
-    if (!t)
+    B->t = tctx_get();
+    if (!B->t)
         return LZO_E_ERROR;
     if (nblocks == 0)
         return LZO_E_OK;
@@ -2178,124 +1109,103 @@ static int batch_common_cb(enum op_kind kind, const uint8_t *const *src, const s
         return LZO_E_OUT_OF_MEMORY;
     }
     for (size_t b = 0; b < nblocks; b++) {
-        if (src_len[b] > 0xFFFFFFF0u) {
+        if (B->src_len[b] > 0xFFFFFFF0u) {
             free(cap);
             free(cost);
             return LZO_E_ERROR;
         }
-        cap[b] = kind == OP_COMPRESS ? lzo_mi355x_worst_compress(src_len[b]) : gc ? gc->cap[b]
-                 : cr ? (size_t)cr->want[b] : lk ? lk->cap[b] : dst_len[b];
+        cap[b] = ops->cap(B, b);
         if (cap[b] > 0xFFFFFFF0u)
             cap[b] = 0xFFFFFFF0u;
-        cost[b] = src_len[b] + cap[b];
-        if (cr)                                 /* the chunk budget counts the slices too */
-            for (size_t k = cr->req_first[b]; k < cr->req_first[b + 1]; k++)
-                cost[b] += cr_slot(cr, b, k);
-        if (lk)                                 /* and the requests, their names and their results */
-            for (size_t k = lk->req_first[b]; k < lk->req_first[b + 1]; k++)
-                cost[b] += sizeof(struct pom_lookup_req) + 12 + POM_LK_REC_SIZE +
-                           lk_name_bytes(lk, &lk->req[lk->req_ids[k]]);
+        cost[b] = B->src_len[b] + cap[b] + (ops->extra_cost ? ops->extra_cost(B, b) : 0);
     }
-    struct hbatch B = {kind, src, src_len, dst, dst_len, status, cap, cost,
-                       kind == OP_COMPRESS ? kChunkBudgetCompress : kChunkBudget,
-                       {0, 1, NULL, NULL}, devs, t, 0, kSlots, 0, on_chunk, pre_chunk, cb_ctx, gc, cr, lk};
-    B.ooo = kind == OP_COMPRESS && pom_dbg_int("ooo", 1) != 0;
+    B->cap = cap;
+    B->cost = cost;
+    B->budget = ops->largest_first ? kChunkBudgetCompress : kChunkBudget;
+    B->plan = (struct pom_plan){0, 1, NULL, NULL};
+    B->devs = devs;
+    B->nslots = kSlots;
+    B->ooo = ops->largest_first && pom_dbg_int("ooo", 1) != 0;
+    B->small_first = !ops->largest_first && pom_dbg_int("dec_small_first", 1) != 0;
     /* compress chunks that fit the LDS encoder's 4 blocks per CU at once use
      * it: a block alone on its CU finishes twice as fast as with the
      * dictionaries in HBM (that encoder wins only on full GPUs: 16 per CU) */
-    B.enc_lds_max = (uint32_t)pom_dbg_int("enc_lds_max", (long)(lzo_mi355x_fast_resident_blocks() / 4));
+    B->enc_lds_max = (uint32_t)pom_dbg_int("enc_lds_max", (long)(lzo_mi355x_fast_resident_blocks() / 4));
     const long ns = pom_dbg_int("slots", kSlots);
     if (ns >= 1 && ns <= kSlots)
-        B.nslots = (int)ns;
+        B->nslots = (int)ns;
     const long mb = pom_dbg_int("chunk_mb", 0);
     if (mb > 0)
-        B.budget = (size_t)mb << 20;
+        B->budget = (size_t)mb << 20;
     int rc = LZO_E_OUT_OF_MEMORY;
-    if (pom_plan_make(&B.plan, nblocks, cost, ndev, kSplitMinBytes) == 0) {
+    if (pom_plan_make(&B->plan, nblocks, cost, ndev, kSplitMinBytes) == 0) {
         /* blocks a failed device leaves untouched read as errors */
         for (size_t b = 0; b < nblocks; b++) {
-            status[b] = LZO_E_ERROR;
-            if (gc)
-                gc->err[b] = LZO_E_ERROR;
-            else if (!cr && !lk)                /* (a column read's and a lookup's requests: set by the caller) */
-                dst_len[b] = 0;
+            B->status[b] = LZO_E_ERROR;
+            if (ops->unreached)
+                ops->unreached(B, b);
         }
-        rc = pom_run_devices(B.plan.ndev, dev_run, &B) == 0 ? LZO_E_OK : LZO_E_ERROR;
+        rc = pom_run_devices(B->plan.ndev, dev_run, B) == 0 ? LZO_E_OK : LZO_E_ERROR;
         if (g_timing)
-            fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n",
-                    kind == OP_COMPRESS ? "compress" : kind == OP_READDIR ? "readdir" : kind == OP_KVLIST ? "kvlist" : lk ? "lookup" : gc ? "gc scan" : cr ? "column read" : "decompress",
-                    nblocks, B.plan.ndev,
+            fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n", ops->label, nblocks, B->plan.ndev,
                     now_ms() - t0);
-        pom_plan_free(&B.plan);
+        pom_plan_free(&B->plan);
     }
     free(cap);
     free(cost);
     return rc;
 }
 
-int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                        struct pom_gc_sink *sink)
+static int codec_batch(const struct chunk_ops *ops, const uint8_t *const *src, const size_t *src_len,
+                       uint8_t *const *dst, size_t *dst_len, int *status, size_t nblocks,
+                       pom_chunk_fn on_chunk, pom_chunk_fn pre_chunk, void *cb_ctx)
 {
-    for (size_t b = 0; b < nblocks; b++) {
-        sink->out_len[b] = sink->live[b] = sink->nranges[b] = 0;
-        sink->rng[b] = NULL;
-    }
-    return batch_common_cb(OP_GC_SCAN, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL, NULL);
+    struct hbatch B = {.ops = ops, .src = src, .src_len = src_len, .dst = dst, .dst_len = dst_len,
+                       .status = status, .on_chunk = on_chunk, .pre_chunk = pre_chunk, .cb_ctx = cb_ctx};
+    return pom_host_batch(&B, nblocks);
 }
 
-int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                        struct pom_gc_sink *sink)
+/* lzo_mi355x_decompress_batch with pre_chunk(ctx, ids, nb) called before each
+ * chunk's inputs are staged: the caller fills src[ids[i]] (src_len is known
+ * up front) while earlier chunks are on the GPU.  Same threads as
+ * pom_compress_batch_chunked. */
+int pom_decompress_batch_chunked(const uint8_t *const *src, const size_t *src_len, uint8_t *const *dst,
+                                 size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn pre_chunk,
+                                 void *ctx)
 {
-    for (size_t b = 0; b < nblocks; b++) {
-        sink->out_len[b] = sink->live[b] = sink->nranges[b] = sink->bytes[b] = 0;
-        sink->dents[b] = NULL;
-    }
-    return batch_common_cb(OP_READDIR, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL, NULL);
+    return codec_batch(&decompress_ops, src, src_len, dst, dst_len, status, nblocks, NULL, pre_chunk, ctx);
 }
 
-int pom_kvlist_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                       struct pom_gc_sink *sink)
+/* lzo_mi355x_compress_batch with on_chunk(ctx, ids, nb) called as each chunk's
+ * blocks (ids into the caller's arrays) are delivered -- from the thread
+ * running that device's chunks, so concurrently for batches split over
+ * several GPUs. */
+int pom_compress_batch_chunked(const uint8_t *const *src, const size_t *src_len, uint8_t *const *dst,
+                               size_t *dst_len, int *status, size_t nblocks, pom_chunk_fn on_chunk,
+                               void *ctx)
 {
-    for (size_t b = 0; b < nblocks; b++) {
-        sink->out_len[b] = sink->live[b] = sink->nranges[b] = sink->bytes[b] = sink->keybytes[b] = 0;
-        sink->dents[b] = NULL;
-    }
-    return batch_common_cb(OP_KVLIST, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, sink, NULL, NULL);
-}
-
-int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                         struct pom_col_sink *sink)
-{
-    return batch_common_cb(OP_COL_READ, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, NULL,
-                           sink, NULL);
-}
-
-int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                       struct pom_lookup_sink *sink)
-{
-    return batch_common_cb(OP_LOOKUP, src, src_len, NULL, NULL, sink->status, nblocks, NULL, NULL, NULL, NULL,
-                           NULL, sink);
+    return codec_batch(&compress_ops, src, src_len, dst, dst_len, status, nblocks, on_chunk, NULL, ctx);
 }
 
 int lzo_mi355x_compress_batch(const uint8_t *const *src, const size_t *src_len,
                               uint8_t *const *dst, size_t *dst_len, int *status,
                               size_t nblocks)
 {
-    return batch_common(OP_COMPRESS, src, src_len, dst, dst_len, status, nblocks);
+    return codec_batch(&compress_ops, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL);
 }
 
 int lzo_mi355x_decompress_batch(const uint8_t *const *src, const size_t *src_len,
                                 uint8_t *const *dst, size_t *dst_len, int *status,
                                 size_t nblocks)
 {
-    return batch_common(OP_DECOMPRESS, src, src_len, dst, dst_len, status, nblocks);
+    return codec_batch(&decompress_ops, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL);
 }
 
 int lzo_mi355x_decompress_concat_batch(const uint8_t *const *src, const size_t *src_len,
                                        uint8_t *const *dst, size_t *dst_len, int *status,
                                        size_t nblocks)
 {
-    return batch_common(OP_CONCAT, src, src_len, dst, dst_len, status, nblocks);
+    return codec_batch(&concat_ops, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -166,37 +166,42 @@ int lzo_mi355x_launch_gc_scan(const uint8_t *payload, const uint64_t *payload_of
                               struct pom_gc_range *ranges, uint64_t ranges_cap, int32_t *err,
                               hipStream_t stream);
 
-/* Host side (lzo_host.c), not part of the ABI: the chunk pipeline of the host
- * batches with the walk queued behind each chunk's decode (gc_scan.c).  Block
- * b is src_len[b] bytes at src[b]: an LZO1X stream decoded on the GPU with
- * capacity cap[b] when is_lzo[b], else a payload walked as staged.  Per block
- * the decoder's status and out_len (0 and src_len[b] when not is_lzo), and
- * live, nranges and err as pom_gc_scan_dev; rng[b] = the block's nranges[b]
- * ranges, inside one of the per-chunk buffers linked at bufs (the caller
- * frees them with pom_gc_sink_free).  No decoded byte is copied back. */
-struct pom_gc_buf;
-struct pom_gc_sink {
+/* Host side (host_records.c), not part of the ABI: the chunk pipeline of the
+ * host batches with a walk queued behind each chunk's decode (gc_scan.c,
+ * readdir.c, kvlist.c).  Block b is src_len[b] bytes at src[b]: an LZO1X
+ * stream decoded on the GPU with capacity cap[b] when is_lzo[b], else a
+ * payload walked as staged.  Per block the decoder's status and out_len (0 and
+ * src_len[b] when not is_lzo), and live, count and err as the walk's _dev call
+ * gives them; recs[b] = the block's records, inside one of the per-chunk
+ * buffers linked at bufs (the caller frees them with pom_walk_sink_free).
+ * Only the counts and the records are copied back. */
+struct pom_walk_buf;
+struct pom_walk_sink {
     const uint8_t *is_lzo;
     const size_t *cap;
     const uint8_t *adepth;
-    int column;
     int32_t *status, *err;
-    uint32_t *out_len, *live, *nranges;
-    const struct pom_gc_range **rng;
-    uint32_t *bytes;                /* pom_readdir_chunked only */
-    const uint8_t **dents;          /* pom_readdir_chunked only */
+    uint32_t *out_len, *live;
+    uint32_t *count;                /* nranges (GC scan) or dnum (listings) */
+    const uint8_t **recs;           /* count[b] 16-byte ranges (GC scan) or bytes[b] bytes (listings) */
+    int column;                     /* pom_gc_scan_chunked only */
+    uint32_t *bytes;                /* the listings only */
     /* pom_kvlist_chunked only: */
     uint32_t *keybytes;
     uint64_t *mask;                 /* 16 words a block, or NULL: the masks stay on the device */
     uint32_t kv_op, needle_len;
-    const uint8_t *needle;
-    int count_only;                 /* no emit launch, no record comes back */
-    struct pom_gc_buf *bufs;
+    const uint8_t *needle;          /* staged once per chunk */
+    int count_only;                 /* no emit launch, no record comes back (recs[b] stays NULL) */
+    struct pom_walk_buf *bufs;
     pthread_mutex_t mu;             /* bufs: chunks of a multi-GPU batch finish on several threads */
 };
 int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                        struct pom_gc_sink *sink);
-void pom_gc_sink_free(struct pom_gc_sink *sink);
+                        struct pom_walk_sink *sink);
+int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                        struct pom_walk_sink *sink);
+int pom_kvlist_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                       struct pom_walk_sink *sink);
+void pom_walk_sink_free(struct pom_walk_sink *sink);
 
 /* Host side (gc_scan.c), not part of the ABI: the header checks the walks'
  * host batches share (include/pom_gc.h pom_gc_scan_batch).  0 and the block a
@@ -211,6 +216,45 @@ struct pom_walk_block {
 };
 int pom_itb_walk_header(const uint8_t *rec, size_t rec_len, struct pom_walk_block *w);
 
+/* Host side (gc_scan.c), not part of the ABI: the two halves the walks' host
+ * batches share around their pom_*_chunked call.  pom_walk_out names the
+ * caller's outputs: out_cap and first[] count units of `unit` bytes (16-byte
+ * ranges, or bytes); dnum, keybytes, mask, len_ok and entries_ok may be NULL.
+ * listing: the h.entries rule of the listings (negative: -EINVAL; 0: done, not
+ * walked), their records sized by bytes[] and copied over the copy threads.
+ * count_only: nothing is copied and nothing can run out of room. */
+struct pom_walk_out {
+    uint8_t *out;
+    size_t out_cap, unit;
+    size_t *first;
+    uint32_t *live, *dnum, *keybytes;
+    uint64_t *mask;
+    int *err, *len_ok, *entries_ok;
+    int listing, count_only;
+};
+/* The work arrays of one call: the records that go to the GPU are k = 0 ... m -
+ * 1, record idx[k], and G is their sink, set up but for the operation's own
+ * inputs (column; op and needle). */
+struct pom_walk_batch {
+    size_t n, m;
+    size_t *idx, *slen, *cap, *fit;
+    const uint8_t **src, **recs;
+    uint8_t *flags, **to;
+    int32_t *i32, *entries;
+    uint32_t *u32;
+    uint64_t *masks;
+    struct pom_walk_sink G;
+};
+/* Zeroes the outputs, selects the records by their headers and sets up the
+ * sink.  LZO_E_OK or LZO_E_OUT_OF_MEMORY; pom_walk_finish follows either way. */
+int pom_walk_begin(struct pom_walk_batch *W, const uint8_t *const *rec, const size_t *rec_len, size_t n,
+                   const struct pom_walk_out *O);
+/* rc: pom_walk_begin's or the chunked call's.  A failure gives every selected
+ * record LZO_E_ERROR; otherwise the results are put together in ITB order.
+ * Frees everything and returns the batch's result (rc, LZO_E_OK or
+ * POM_GC_E_NOSPACE). */
+int pom_walk_finish(struct pom_walk_batch *W, int rc, const struct pom_walk_out *O);
+
 /* The directory listing's ITB walk (itb_dents.hip): pom_readdir_dev of
  * include/pom_readdir.h, three launches on `stream`. */
 int lzo_mi355x_launch_readdir(const uint8_t *payload, const uint64_t *payload_off,
@@ -218,15 +262,6 @@ int lzo_mi355x_launch_readdir(const uint8_t *payload, const uint64_t *payload_of
                               const uint8_t *adepth, uint32_t nitb, uint32_t *live,
                               uint32_t *dnum, uint32_t *bytes, uint64_t *first, uint8_t *out,
                               uint64_t out_cap, int32_t *err, hipStream_t stream);
-
-/* Host side (lzo_host.c), not part of the ABI: pom_gc_scan_chunked's pipeline
- * with the dentry walk in the range walk's place (readdir.c).  The sink is the
- * same, read as follows: column and rng are unused, nranges[b] = the block's
- * dnum, bytes[b] its record bytes, and dents[b] points at them, inside one of
- * the per-chunk buffers linked at bufs.  Only the counts and the records are
- * copied back. */
-int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                        struct pom_gc_sink *sink);
 
 /* The key/value table listing's ITB walk (itb_keys.hip): pom_kvlist_dev of
  * include/pom_kvlist.h, three launches on `stream`. */
@@ -237,16 +272,6 @@ int lzo_mi355x_launch_kvlist(const uint8_t *payload, const uint64_t *payload_off
                              uint32_t *keybytes, uint64_t *mask, uint64_t *first, uint8_t *out,
                              uint64_t out_cap, int32_t *err, hipStream_t stream);
 
-/* Host side (lzo_host.c), not part of the ABI: pom_readdir_chunked's pipeline
- * with the key walk in the dentry walk's place (kvlist.c).  The sink is read
- * as pom_readdir_chunked reads it (nranges[b] = the block's dnum, bytes[b] its
- * record bytes, dents[b] points at them), plus keybytes[b], the masks when
- * mask is given, and the call's op and needle, which is staged once per
- * chunk.  With count_only no record is emitted or copied back (dents[b] stays
- * NULL).  Only the counts, the masks asked for and the records come back. */
-int pom_kvlist_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                       struct pom_gc_sink *sink);
-
 /* Column reads by offset and size (col_slice.hip): pom_col_slice_dev of
  * include/pom_column.h, one launch on `stream`. */
 struct pom_col_req;
@@ -256,7 +281,7 @@ int lzo_mi355x_launch_col_slice(const uint8_t *data, const uint64_t *data_off,
                                 uint32_t nreq, uint8_t *out, const uint64_t *out_off,
                                 uint32_t *out_len, int32_t *err, hipStream_t stream);
 
-/* Host side (lzo_host.c), not part of the ABI: the chunk pipeline of the host
+/* Host side (host_records.c), not part of the ABI: the chunk pipeline of the host
  * batches with the region copy queued behind each chunk's decode
  * (column_codec.c).  Block b is an LZO1X stream of src_len[b] bytes at src[b],
  * decoded on the GPU with capacity want[b] (concat: as consecutive streams);
@@ -286,7 +311,7 @@ int lzo_mi355x_launch_lookup(const uint8_t *payload, const uint64_t *payload_off
                              uint32_t nreq, const uint8_t *names, uint32_t names_len, int32_t *err,
                              uint32_t *nr, uint32_t *depth, uint8_t *out, hipStream_t stream);
 
-/* Host side (lzo_host.c), not part of the ABI: pom_gc_scan_chunked's pipeline
+/* Host side (host_records.c), not part of the ABI: pom_gc_scan_chunked's pipeline
  * (LZO records decoded, stored ones walked as staged) with the lookup behind
  * each chunk's decode and pom_col_read_chunked's request grouping (lookup.c).
  * Block b's requests are req[req_ids[k]] for k in [req_first[b], req_first[b +

@@ -267,15 +267,49 @@ def test_read_unreferenced_damaged_column(zipped):
     read_and_check([cols[0], b"", b"", cols[3], b""], stored, [(3, 5, 100), (0, 99000, 5000), (3, 0, U64)])
 
 
-def test_read_spans_chunks(dev, debug_env):
-    """chunk_mb=1: 40 columns of 100 KiB take several chunks; three shuffled
-    requests each, so a chunk delivers requests from all over the caller's
-    arrays."""
+@pytest.fixture(scope="module")
+def chunky(dev):
+    """40 columns of 100 KiB with three shuffled requests each: several chunks
+    under chunk_mb=1.  (cols, zips, reqs)."""
     cols = [bytes(synth.block(synth.ITB, 1000 + i, 100 * 1024)) for i in range(40)]
     zips, comp = column.zip_batch(cols)
     assert comp == [1] * 40
     rnd = random.Random(40)
     reqs = [(c, rnd.randrange(100 * 1024), rnd.randrange(1, 64 * 1024)) for c in range(40) for _ in range(3)]
     rnd.shuffle(reqs)
+    return cols, zips, reqs
+
+
+def test_read_spans_chunks(chunky, debug_env):
+    """chunk_mb=1: 40 columns of 100 KiB take several chunks; three shuffled
+    requests each, so a chunk delivers requests from all over the caller's
+    arrays."""
+    cols, zips, reqs = chunky
+    debug_env("chunk_mb=1")
+    read_and_check(cols, zips, reqs)
+
+
+def test_read_failed_chunk(chunky, debug_env):
+    """fail_chunk=1: the device's second chunk delivery fails as a failed GPU
+    stream would.  The call returns LZO_E_ERROR; a request either reads
+    LZO_E_ERROR or has the unfailed run's result, and both kinds occur; the
+    same call succeeds in full afterwards (the slots are reusable)."""
+    import ctypes
+    cols, zips, reqs = chunky
+    n, nr = len(zips), len(reqs)
+    src = [ctypes.create_string_buffer(z, len(z)) for z in zips]
+    zl = (ctypes.c_size_t * n)(*[len(z) for z in zips])
+    rq = (column.Req * nr)(*[column.Req(o, s, c, 0) for c, o, s in reqs])
+    out = [ctypes.create_string_buffer(s) for _, _, s in reqs]
+    ol = (ctypes.c_size_t * nr)(*[7] * nr)
+    err = (ctypes.c_int * nr)(*[7] * nr)
+    debug_env("chunk_mb=1,fail_chunk=1")
+    rc = column._lib().pom_col_read_batch(column._arr(src), zl, n, rq, nr, column._arr(out), ol, err)
+    assert rc == lzo.LZO_E_ERROR
+    lost = [r for r in range(nr) if err[r] == lzo.LZO_E_ERROR]
+    assert 0 < len(lost) < nr
+    for r, (c, o, s) in enumerate(reqs):
+        if r not in lost:
+            assert err[r] == 0 and out[r].raw[: ol[r]] == cols[c][o: o + s], (r, reqs[r])
     debug_env("chunk_mb=1")
     read_and_check(cols, zips, reqs)

@@ -295,10 +295,11 @@ def test_batch_itbid_check_and_just_split(oracle, families):
     assert (res.err.tolist(), res.depth.tolist(), res.out.any()) == ([U.ESPLIT], [0], False)
 
 
-def test_batch_spans_chunks(oracle, families, debug_env, monkeypatch):
-    """chunk_mb=1: about 50 KB a record, so 60 records take several chunks, on
-    one GPU and on every visible one; the chunks reorder the blocks (smallest
-    first, LZO before stored) and the results still come in request order."""
+@pytest.fixture(scope="module")
+def chunky(oracle):
+    """60 records of about 50 KB, every fourth stored uncompressed, with
+    shuffled requests to all of them: several chunks under chunk_mb=1.
+    (stored, req, names, want)."""
     recs, items = [], []
     for b in range(60):
         n_ites = 60 + 7 * (b % 9)
@@ -306,10 +307,45 @@ def test_batch_spans_chunks(oracle, families, debug_env, monkeypatch):
         recs.append(rec)
         items += U.hits_for(rec, b, range(b % 4, n_ites, 4)) + U.misses_for(rec, b, b % n_ites)
     req, names = lookup.requests(items)
-    req = req[np.random.default_rng(11).permutation(len(req))]
+    req = np.ascontiguousarray(req[np.random.default_rng(11).permutation(len(req))])
     want = U.expect([U.payload_of(r) for r in recs], [8] * 60, req, names)
-    stored = [r if b % 4 == 1 else U.lzo_record(oracle, r) for b, r in enumerate(recs)]
+    return [r if b % 4 == 1 else U.lzo_record(oracle, r) for b, r in enumerate(recs)], req, names, want
+
+
+def test_batch_spans_chunks(chunky, debug_env, monkeypatch):
+    """chunk_mb=1: about 50 KB a record, so 60 records take several chunks, on
+    one GPU and on every visible one; the chunks reorder the blocks (smallest
+    first, LZO before stored) and the results still come in request order."""
+    stored, req, names, want = chunky
     debug_env("chunk_mb=1")
     same(lookup.lookup_batch(stored, req, names), want)
     monkeypatch.setenv("POM_LZO_DEVICES", "0")
+    same(lookup.lookup_batch(stored, req, names), want)
+
+
+def test_batch_failed_chunk(chunky, debug_env):
+    """fail_chunk=1: the device's second chunk delivery fails as a failed GPU
+    stream would.  The call returns LZO_E_ERROR; a request either reads
+    LZO_E_ERROR with a zeroed record or has the unfailed run's result, and both
+    kinds occur; the same call succeeds in full afterwards (the slots are
+    reusable)."""
+    import ctypes
+    stored, req, names, want = chunky
+    n, nreq = len(stored), len(req)
+    bufs = [np.frombuffer(r, dtype=np.uint8) for r in stored]
+    ptrs = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (ctypes.c_size_t * n)(*[b.size for b in bufs])
+    blob = np.frombuffer(names, dtype=np.uint8)
+    out = np.full((nreq, lookup.REC_SIZE), 7, dtype=np.uint8)
+    err = np.full(nreq, 7, dtype=np.int32)
+    nr, depth = (np.full(nreq, 7, dtype=np.uint32) for _ in range(2))
+    debug_env("chunk_mb=1,fail_chunk=1")
+    rc = lookup._lib().pom_lookup_batch(ptrs, lens, n, 0, req.ctypes.data, nreq, blob.ctypes.data, len(names),
+                                        out.ctypes.data, err.ctypes.data, nr.ctypes.data, depth.ctypes.data)
+    assert rc == lzo.LZO_E_ERROR
+    lost = err == lzo.LZO_E_ERROR
+    assert 0 < lost.sum() < nreq and not out[lost].any()
+    kept = ~lost
+    same((err[kept], nr[kept], depth[kept], out[kept]), tuple(w[kept] for w in want))
+    debug_env("chunk_mb=1")
     same(lookup.lookup_batch(stored, req, names), want)

@@ -419,14 +419,53 @@ def test_batch_nospace_then_retry(many):
     check_batch(stored[:40], payloads, [2] * 40, out_cap=0)
 
 
-def test_batch_spans_chunks(oracle, debug_env):
+@pytest.fixture(scope="module")
+def chunky(oracle):
+    """60 records of about 50 KB, every fourth stored uncompressed: several
+    chunks under chunk_mb=1."""
+    recs = [make_record(900 + i, 20 + 7 * (i % 9), 8, range(0, 20 + 7 * (i % 9), 1 + i % 3)) for i in range(60)]
+    return recs, [r if i % 4 == 1 else lzo_record(oracle, r) for i, r in enumerate(recs)]
+
+
+def test_batch_spans_chunks(chunky, debug_env):
     """chunk_mb=1: about 50 KB a record, so 60 records take several chunks;
     the chunks reorder the blocks (smallest first, LZO before stored) and the
     records still come out in ITB order."""
-    recs = [make_record(900 + i, 20 + 7 * (i % 9), 8, range(0, 20 + 7 * (i % 9), 1 + i % 3)) for i in range(60)]
-    stored = [r if i % 4 == 1 else lzo_record(oracle, r) for i, r in enumerate(recs)]
+    recs, stored = chunky
     debug_env("chunk_mb=1")
     check_batch(stored, [payload_of(r) for r in recs], [8] * 60)
+
+
+def test_batch_failed_chunk(chunky, debug_env):
+    """fail_chunk=1: the device's second chunk delivery fails as a failed GPU
+    stream would.  The call returns LZO_E_ERROR, every record that went to the
+    GPU reads LZO_E_ERROR with live == dnum == 0, a bad header keeps -EINVAL
+    and a record with no entries its 0, and the same call succeeds in full
+    afterwards (the slots are reusable)."""
+    import ctypes
+    recs, stored = chunky[0], list(chunky[1])
+    stored.insert(30, recs[0][:200])                            # no whole header
+    stored.insert(45, make_record(990, 3, 2, [0, 1, 2], entries=0))
+    payloads = [payload_of(r) for r in recs]
+    payloads.insert(30, None)
+    payloads.insert(45, None)
+    n = len(stored)
+    bufs = [np.frombuffer(r, dtype=np.uint8) for r in stored]
+    ptrs = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (ctypes.c_size_t * n)(*[b.size for b in bufs])
+    out = np.zeros(1 << 20, dtype=np.uint8)
+    first = np.zeros(n + 1, dtype=np.uint64)
+    live, dnum = (np.full(n, 7, dtype=np.uint32) for _ in range(2))
+    err, len_ok, entries_ok = (np.full(n, 7, dtype=np.int32) for _ in range(3))
+    debug_env("chunk_mb=1,fail_chunk=1")
+    rc = readdir._lib().pom_readdir_batch(ptrs, lens, n, out.ctypes.data, out.size, first.ctypes.data,
+                                          live.ctypes.data, dnum.ctypes.data, err.ctypes.data, len_ok.ctypes.data,
+                                          entries_ok.ctypes.data)
+    assert rc == lzo.LZO_E_ERROR
+    assert err.tolist() == [EINVAL if b == 30 else 0 if b == 45 else lzo.LZO_E_ERROR for b in range(n)]
+    assert not live.any() and not dnum.any()
+    debug_env("chunk_mb=1")
+    check_batch(stored, payloads, [8] * n, want_err={30: EINVAL, 45: 0})
 
 
 def test_batch_synth_names(oracle):
