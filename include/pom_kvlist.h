@@ -17,10 +17,10 @@
  *   pom_kvlist_batch  <- the same over stored records, decoded on the GPU
  *                        (records in host memory)
  *
- * The INDEX_DTRIG triggers (itb_readdir_dtriggered), the reply's allocation
- * and its zero tail, and the INDEX_KV branches of ite_match and of the
- * lookup's copy (mds/itb.c:1095-1116, :1808-1810: hvfs_get / hvfs_sget) stay
- * with the caller.
+ * The INDEX_DTRIG triggers (itb_readdir_dtriggered) and the reply's allocation
+ * and its zero tail stay with the caller.  The INDEX_KV branches of ite_match
+ * and of the lookup's copy (mds/itb.c:1095-1116, :1808-1810: hvfs_get /
+ * hvfs_sget) are pom_kvget.h's.
  */
 #ifndef POM_KVLIST_H
 #define POM_KVLIST_H 1

@@ -17,8 +17,8 @@
  *                        with the header's two rules (:1753-1767, :2030-2033)
  *
  * Everything that writes stays with the caller: create, unlink, update, link,
- * the lease acquire and release and the INDEX_INTENT_* lease setup; so do the
- * INDEX_KV branches and itb_search_dtriggered.  The lease word mdu.dtime is
+ * the lease acquire and release and the INDEX_INTENT_* lease setup; so does
+ * itb_search_dtriggered.  The INDEX_KV branches are pom_kvget.h's.  The lease word mdu.dtime is
  * inside the returned MDU bytes (record byte 8 + POM_MDU_DTIME_OFF), so the
  * caller runs ite_lease_check_setup's read-only tests (:1688-1708) on the
  * record.

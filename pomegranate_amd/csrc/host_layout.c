@@ -5,6 +5,7 @@
 
 #include "host_layout.h"
 #include "pom_column.h"
+#include "pom_kvget.h"
 #include "pom_kvlist.h"
 #include "pom_lookup.h"
 
@@ -164,5 +165,44 @@ void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nl
     o += out;
     L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
     K->o_res = take(&o, K->res_bytes);
+    L->dtotal = o;
+}
+
+void pom_layout_kvget(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, size_t nreq, size_t keys_bytes, int records, size_t scratch)
+{
+    size_t in, out, o = 0, r = 8;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct kvget_layout *K = &L->u.kg;
+    K->nreq = nreq;
+    K->keys_bytes = keys_bytes;
+    K->rcap = records ? POM_ALIGN_UP(POM_KG_REC_MAX * nreq, 16) : 0;
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    K->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_req = take(&o, sizeof(struct pom_kvget_req) * nreq);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    L->o_status = take(&o, 4 * nb);
+    L->o_outlen = take(&o, 4 * nb);
+    K->scan.o_adepth = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    K->o_keys = take(&o, POM_ALIGN_UP(keys_bytes, 256));
+    L->o_dst = o;
+    K->r_err = take(&r, 4 * nreq);
+    K->r_nr = take(&r, 4 * nreq);
+    K->r_depth = take(&r, 4 * nreq);
+    K->r_len = take(&r, 4 * nreq);
+    K->r_lease = take(&r, 8 * nreq);
+    K->res_bytes = r;
+    K->o_hres = o;
+    K->o_hrec = POM_ALIGN_UP(o + K->res_bytes, 16);
+    L->htotal = K->o_hrec + K->rcap;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_first = take(&o, 8 * nreq);
+    K->o_res = take(&o, POM_ALIGN_UP(K->res_bytes, 256));
+    K->o_pack = take(&o, K->rcap);
     L->dtotal = o;
 }

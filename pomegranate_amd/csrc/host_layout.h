@@ -90,6 +90,24 @@ struct lookup_layout {
     size_t res_hdr, res_bytes;
 };
 
+/* Key/value gets.  The lookup's inputs with the key blob in the names' place.
+ * The fixed-size results lie alike on both sides behind the chunk's record
+ * total (on the device the last entry of first[]), and come back in one copy;
+ * the packed records follow in a second one, sized by that total. */
+struct kvget_layout {
+    struct scan_layout scan;
+    size_t nreq, keys_bytes;
+    size_t o_req;               /* struct pom_kvget_req per request */
+    size_t o_keys;              /* the chunk's own key blob, behind the inputs */
+    size_t o_first;             /* device only: u64, nreq + 1; first[nreq] is the results' first word */
+    size_t o_res, o_hres;       /* [total u64][err][nr][depth][len][lease] */
+    size_t r_err, r_nr, r_depth, r_len;     /* i32, u32, u32, u32 per request */
+    size_t r_lease;             /* u64 per request */
+    size_t res_bytes;
+    size_t rcap;                /* record room, in bytes: 364 a request (0: lengths only) */
+    size_t o_pack, o_hrec;      /* device, host: the packed records */
+};
+
 struct layout {
     size_t nb;
     const size_t *ids;
@@ -108,6 +126,7 @@ struct layout {
         struct walk_layout walk;
         struct col_layout col;
         struct lookup_layout lk;
+        struct kvget_layout kg;
     } u;
 };
 
@@ -123,6 +142,10 @@ void pom_layout_col(struct layout *L, const size_t *ids, size_t nb, const size_t
                     const size_t *cap, size_t nreq, size_t slice_bytes, size_t scratch);
 void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
                        const size_t *cap, size_t nreq, size_t names_bytes, size_t scratch);
+
+/* records != 0: room for every request's longest record on both sides */
+void pom_layout_kvget(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, size_t nreq, size_t keys_bytes, int records, size_t scratch);
 
 /* The ITEs a payload of n bytes can hold: what a walk can emit at the most. */
 size_t pom_walk_max_ites(size_t n);

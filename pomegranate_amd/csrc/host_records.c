@@ -5,8 +5,9 @@
  * (itb_scan.hip), the directory listing (itb_dents.hip), the key/value
  * listing (itb_keys.hip) -- share one layout, one staging and one delivery,
  * told apart by their list of result words and their record unit; the column
- * read (col_slice.hip) and the lookup (itb_find.hip) carry requests.  Their
- * callers (gc_scan.c, readdir.c, kvlist.c, column_codec.c, lookup.c) select
+ * read (col_slice.hip), the lookup (itb_find.hip) and the key/value get
+ * (itb_kvget.hip) carry requests.  Their callers (gc_scan.c, readdir.c,
+ * kvlist.c, column_codec.c, lookup.c, kvget.c) select
  * the blocks and put the results in the caller's order.
  */
 #include <pthread.h>
@@ -17,6 +18,7 @@
 #include "lzo_mi355x.h"
 #include "minilzo.h"
 #include "pom_column.h"
+#include "pom_kvget.h"
 #include "pom_kvlist.h"
 #include "pom_lookup.h"
 
@@ -627,6 +629,204 @@ int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t 
                        struct pom_lookup_sink *sink)
 {
     struct hbatch B = {.ops = &lk_ops, .src = src, .src_len = src_len, .status = sink->status,
+                       .is_lzo = sink->is_lzo, .sink = sink};
+    return pom_host_batch(&B, nblocks);
+}
+
+/* ------------------------------------------------------------------------ */
+/* Key/value gets: decode, chain walk and copy (itb_kvget.hip), values back   */
+/* ------------------------------------------------------------------------ */
+/* The lookups' partition, request order and staging, with the string keys in
+ * the names' place: a string request whose key the caller's blob does not
+ * hold gets no key bytes and a skey_off past the chunk's blob (the kernel's
+ * rule 4 refuses it); one with sklen above 320 gets no key bytes either and
+ * matches nothing.  The records are variable-length, so they come back as the
+ * walks' do: the fixed-size results and the chunk's record total in one copy
+ * queued behind the kernels, exactly that many record bytes in a second one
+ * sized once the first is back.  Staging (host and device alike up to the
+ * inputs' end; pom_layout_kvget):
+ *   [src_off u64][dst_off u64][scan_off u64][requests, nreq][src_len u32][dst_cap u32]
+ *   [status i32][out_len u32][adepth u8]
+ *   [src bytes, 16-B aligned per block][keys]
+ *   device: [decoded payloads][decoder scratch][first u64, nreq]
+ *   both:   [total u64][err i32][nr u32][depth u32][len u32][lease u64], nreq each  <- D2H, one copy
+ *           [the chunk's records, packed, unless lengths only]                    <- D2H, sized after the first
+ * No other decoded byte leaves the device. */
+struct pom_kvget_buf {
+    struct pom_kvget_buf *next;
+    uint64_t pad;
+    uint8_t bytes[];
+};
+
+static int kg_key_ok(const struct pom_kvget_sink *K, const struct pom_kvget_req *q)
+{
+    return (q->kvflag & POM_KV_STR) && q->sklen <= POM_KV_VALUE_MAX && (size_t)q->skey_off + q->sklen <= K->keys_len;
+}
+
+static size_t kg_key_bytes(const struct pom_kvget_sink *K, const struct pom_kvget_req *q)
+{
+    return kg_key_ok(K, q) ? q->sklen : 0;
+}
+
+static size_t kg_cap(const struct hbatch *B, size_t b)
+{
+    const struct pom_kvget_sink *K = B->sink;
+    return K->cap[b];
+}
+
+static size_t kg_keys(const struct pom_kvget_sink *K, size_t b)
+{
+    size_t n = 0;
+    for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++)
+        n += kg_key_bytes(K, &K->req[K->req_ids[k]]);
+    return n;
+}
+
+/* the chunk budget counts the requests, their keys, their results and their records' room */
+static size_t kg_extra_cost(const struct hbatch *B, size_t b)
+{
+    const struct pom_kvget_sink *K = B->sink;
+    return (K->req_first[b + 1] - K->req_first[b]) *
+               (sizeof(struct pom_kvget_req) + 4 * sizeof(uint32_t) + 2 * sizeof(uint64_t) +
+                (K->lengths_only ? 0 : POM_KG_REC_MAX)) + kg_keys(K, b);
+}
+
+static void kg_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    const struct pom_kvget_sink *K = B->sink;
+    size_t nreq = 0, keys = 0;
+    for (size_t i = 0; i < nb; i++) {
+        nreq += K->req_first[ids[i] + 1] - K->req_first[ids[i]];
+        keys += kg_keys(K, ids[i]);
+    }
+    pom_layout_kvget(L, ids, nb, nlzo, B->src_len, B->cap, nreq, keys, !K->lengths_only,
+                     lzo_mi355x_decompress_scratch((uint32_t)nlzo));
+}
+
+static int kg_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    const struct pom_kvget_sink *K = B->sink;
+    const struct kvget_layout *Y = &L->u.kg;
+    if (Y->nreq > 0xFFFFFFFFu / POM_KG_REC_MAX || Y->keys_bytes > 0xFFFFFFF0u)
+        return -1;
+    struct pom_kvget_req *rq = (struct pom_kvget_req *)(h + Y->o_req);
+    uint8_t *ky = h + Y->o_keys;
+    size_t j = 0, at = 0;
+    pom_stage_inputs(L, h, B);
+    stage_scan(L, &Y->scan, h, K->adepth);
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
+            const struct pom_kvget_req *q = &K->req[K->req_ids[k]];
+            const size_t n = kg_key_bytes(K, q);
+            rq[j] = *q;
+            rq[j].itb = (uint32_t)i;            /* the chunk's own ITB index */
+            if (kg_key_ok(K, q)) {
+                rq[j].skey_off = (uint32_t)at;
+                if (n)
+                    memcpy(ky + at, K->keys + q->skey_off, n);
+                at += n;
+            } else {
+                rq[j].skey_off = 0xFFFFFFFFu;   /* outside the chunk's blob (read by string gets of sklen <= 320 only) */
+            }
+        }
+    }
+    return 0;
+}
+
+static int kg_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct kvget_layout *Y = &L->u.kg;
+    uint8_t *d = S->dmem, *res = d + Y->o_res;
+    size_t queued;
+    (void)B;
+    if (pom_decode_lzo_blocks(S, L, 0) != 0)
+        return -1;
+    if (lzo_mi355x_launch_kvget(d, (const uint64_t *)(d + Y->scan.o_scanoff), (const uint32_t *)(d + L->o_outlen),
+                                (const int32_t *)(d + L->o_status), d + Y->scan.o_adepth, (uint32_t)L->nb,
+                                (const struct pom_kvget_req *)(d + Y->o_req), (uint32_t)Y->nreq, d + Y->o_keys,
+                                (uint32_t)Y->keys_bytes, (int32_t *)(res + Y->r_err), (uint32_t *)(res + Y->r_nr),
+                                (uint32_t *)(res + Y->r_depth), (uint32_t *)(res + Y->r_len),
+                                (uint64_t *)(res + Y->r_lease), (uint64_t *)(d + Y->o_first), d + Y->o_pack, Y->rcap,
+                                S->stream) != 0)
+        return -1;
+    return results_back(S, Y->o_hres, Y->o_res, Y->res_bytes, &queued);
+}
+
+/* Once the lengths are back: the D2H of exactly the chunk's records. */
+static int kg_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
+{
+    const struct pom_kvget_sink *K = B->sink;
+    const struct kvget_layout *Y = &L->u.kg;
+    uint64_t total;
+    memcpy(&total, S->hmem + Y->o_hres, 8);
+    if (K->lengths_only)
+        total = 0;
+    if (total > Y->rcap)
+        return -1;
+    if (total && hipMemcpyAsync(S->hmem + Y->o_hrec, S->dmem + Y->o_pack, total, hipMemcpyDeviceToHost, S->stream) !=
+                     hipSuccess)
+        return -1;
+    *packed = total;
+    return 0;
+}
+
+/* The fixed-size results go to their places in the caller's request order;
+ * the records stay in a buffer of the sink until the caller knows the call's
+ * own first[]. */
+static int kg_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    struct pom_kvget_sink *K = B->sink;
+    const struct kvget_layout *Y = &L->u.kg;
+    const uint8_t *res = S->hmem + Y->o_hres;
+    const int32_t *he = (const int32_t *)(res + Y->r_err);
+    const uint32_t *hn = (const uint32_t *)(res + Y->r_nr);
+    const uint32_t *hd = (const uint32_t *)(res + Y->r_depth);
+    const uint32_t *hl = (const uint32_t *)(res + Y->r_len);
+    const uint64_t *hs = (const uint64_t *)(res + Y->r_lease);
+    struct pom_kvget_buf *buf = malloc(sizeof(*buf) + L->packed);
+    if (!buf)
+        return -1;
+    memcpy(buf->bytes, S->hmem + Y->o_hrec, L->packed);
+    size_t j = 0, at = 0;
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        K->status[b] = 0;                       /* delivered; the decoder's code is in the requests' err */
+        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
+            const size_t r = K->req_ids[k];
+            K->err[r] = he[j];
+            K->nr[r] = hn[j];
+            K->depth[r] = hd[j];
+            K->len[r] = hl[j];
+            K->lease[r] = hs[j];
+            K->recs[r] = !K->lengths_only && hl[j] && at + hl[j] <= L->packed ? buf->bytes + at : NULL;
+            at += hl[j];
+        }
+    }
+    pthread_mutex_lock(&K->mu);
+    buf->next = K->bufs;
+    K->bufs = buf;
+    pthread_mutex_unlock(&K->mu);
+    return 0;
+}
+
+void pom_kvget_sink_free(struct pom_kvget_sink *sink)
+{
+    while (sink->bufs) {
+        struct pom_kvget_buf *next = sink->bufs->next;
+        free(sink->bufs);
+        sink->bufs = next;
+    }
+}
+
+/* (a get's requests: set by the caller, so nothing to mark unreached) */
+static const struct chunk_ops kg_ops = {"kvget", 0, kg_cap, kg_extra_cost, NULL, kg_layout,
+                                        kg_stage, kg_kernels, kg_collect, kg_unpack};
+
+int pom_kvget_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                      struct pom_kvget_sink *sink)
+{
+    struct hbatch B = {.ops = &kg_ops, .src = src, .src_len = src_len, .status = sink->status,
                        .is_lzo = sink->is_lzo, .sink = sink};
     return pom_host_batch(&B, nblocks);
 }

@@ -105,20 +105,15 @@ ITB_SCAN_FN bool itb_find_match(const uint8_t* ite, const pom_lookup_req& q, con
 }
 
 // ---------------------------------------------------------------------------
-// The whole walk for one request (rules 2 ... 8; the caller has dealt with
-// req.itb and status).  Returns err; on 0, *nr is the ITE that hit.
+// The chain walk (rules 5, 6 and 8) from index slot `offset`, with the match
+// as a parameter: match(ite) on an ITE that lies inside the payload.  The
+// payload holds the whole index table.  Returns err; on 0, *nr is the ITE
+// that hit.  itb_kvget.h walks with its own match.
 // ---------------------------------------------------------------------------
-ITB_SCAN_FN int32_t itb_find_one(const uint8_t* p, uint32_t n, uint32_t adepth, const pom_lookup_req& q,
-                                 const uint8_t* names, uint32_t names_len, uint32_t* nr, uint32_t* depth)
+template <class Match>
+ITB_SCAN_FN int32_t itb_find_walk(const uint8_t* p, uint32_t n, uint32_t offset, const Match& match, uint32_t* nr,
+                                  uint32_t* depth)
 {
-    *nr = *depth = 0;
-    if (adepth == 0 || adepth > POM_ITB_ADEPTH_MAX)
-        return kItbScanEinval;
-    if (n < POM_ITB_ITE_OFF)
-        return POM_GC_E_TRUNCATED;
-    if (!itb_find_req_ok(q, names_len))
-        return kItbScanEinval;
-    uint32_t offset = (uint32_t)q.hash & ((1u << adepth) - 1u);
     uint32_t d = 0;
     int32_t err = kItbFindEnoent;
     while (offset < POM_ITB_INDEX_ENTRIES) {
@@ -134,7 +129,7 @@ ITB_SCAN_FN int32_t itb_find_one(const uint8_t* p, uint32_t n, uint32_t adepth, 
             err = POM_GC_E_TRUNCATED;
             break;
         }
-        if (itb_find_match(p + POM_ITB_ITE_OFF + POM_ITE_SIZE * s.entry, q, names)) {
+        if (match(p + POM_ITB_ITE_OFF + POM_ITE_SIZE * s.entry)) {
             *nr = s.entry;
             err = 0;
             break;
@@ -145,6 +140,36 @@ ITB_SCAN_FN int32_t itb_find_one(const uint8_t* p, uint32_t n, uint32_t adepth, 
     }
     *depth = d;
     return err;
+}
+
+// (a member function: ITB_SCAN_FN without the CPU build's `static`)
+#ifdef __HIPCC__
+#define ITB_FIND_MEMBER __device__ __forceinline__
+#else
+#define ITB_FIND_MEMBER inline
+#endif
+
+struct itb_find_lookup_match {
+    const pom_lookup_req& q;
+    const uint8_t* names;
+    ITB_FIND_MEMBER bool operator()(const uint8_t* ite) const { return itb_find_match(ite, q, names); }
+};
+
+// ---------------------------------------------------------------------------
+// The whole walk for one request (rules 2 ... 8; the caller has dealt with
+// req.itb and status).  Returns err; on 0, *nr is the ITE that hit.
+// ---------------------------------------------------------------------------
+ITB_SCAN_FN int32_t itb_find_one(const uint8_t* p, uint32_t n, uint32_t adepth, const pom_lookup_req& q,
+                                 const uint8_t* names, uint32_t names_len, uint32_t* nr, uint32_t* depth)
+{
+    *nr = *depth = 0;
+    if (adepth == 0 || adepth > POM_ITB_ADEPTH_MAX)
+        return kItbScanEinval;
+    if (n < POM_ITB_ITE_OFF)
+        return POM_GC_E_TRUNCATED;
+    if (!itb_find_req_ok(q, names_len))
+        return kItbScanEinval;
+    return itb_find_walk(p, n, (uint32_t)q.hash & ((1u << adepth) - 1u), itb_find_lookup_match{q, names}, nr, depth);
 }
 
 // ---------------------------------------------------------------------------

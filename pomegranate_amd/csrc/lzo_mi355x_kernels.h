@@ -336,6 +336,45 @@ struct pom_lookup_sink {
 int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                        struct pom_lookup_sink *sink);
 
+/* The key/value point get's ITB walk (itb_kvget.hip): pom_kvget_dev of
+ * include/pom_kvget.h, three launches on `stream`. */
+struct pom_kvget_req;
+int lzo_mi355x_launch_kvget(const uint8_t *payload, const uint64_t *payload_off,
+                            const uint32_t *payload_len, const int32_t *status,
+                            const uint8_t *adepth, uint32_t nitb, const struct pom_kvget_req *req,
+                            uint32_t nreq, const uint8_t *keys, uint32_t keys_len, int32_t *err,
+                            uint32_t *nr, uint32_t *depth, uint32_t *len, uint64_t *lease,
+                            uint64_t *first, uint8_t *out, uint64_t out_cap, hipStream_t stream);
+
+/* Host side (host_records.c), not part of the ABI: pom_lookup_chunked's
+ * partition, request grouping and key staging (kvget.c) with the get behind
+ * each chunk's decode.  Per request err, nr, depth, len and lease in the
+ * caller's request order.  The records are variable-length: each chunk's come
+ * back packed, in the chunk's own request order, into a buffer linked at bufs,
+ * and recs[r] points at request r's (NULL when lengths_only, or len[r] == 0);
+ * the caller places them and frees the buffers with pom_kvget_sink_free. */
+struct pom_kvget_buf;
+struct pom_kvget_sink {
+    const uint8_t *is_lzo;
+    const size_t *cap;
+    const uint8_t *adepth;
+    const size_t *req_first, *req_ids;
+    const struct pom_kvget_req *req;
+    const uint8_t *keys;
+    size_t keys_len;
+    int lengths_only;               /* no emit launch, no record comes back */
+    int *err;
+    uint32_t *nr, *depth, *len;
+    uint64_t *lease;
+    const uint8_t **recs;
+    int32_t *status;
+    struct pom_kvget_buf *bufs;
+    pthread_mutex_t mu;             /* bufs: chunks of a multi-GPU batch finish on several threads */
+};
+int pom_kvget_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                      struct pom_kvget_sink *sink);
+void pom_kvget_sink_free(struct pom_kvget_sink *sink);
+
 #ifdef __cplusplus
 }
 #endif

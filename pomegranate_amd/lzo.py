@@ -69,6 +69,8 @@ EXPORTS = (
     "pom_lookup_dev", "pom_lookup_batch",
     # include/pom_kvlist.h
     "pom_kvlist_dev", "pom_kvlist_batch",
+    # include/pom_kvget.h
+    "pom_kvget_dev", "pom_kvget_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
