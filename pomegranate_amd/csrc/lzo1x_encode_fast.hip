@@ -36,6 +36,7 @@
 
 #include "lzo_mi355x_kernels.h"
 #include "lzo1x_emit.h"
+#include "lzo1x_enc_group.h"
 #include "lzo1x_enc_rebase.h"
 #include "lzo1x_wave.h"
 
@@ -54,7 +55,7 @@ constexpr uint32_t kSlots = emit::kSlots;
 static_assert(ENC_REBASE_BACK == 0xBFFF + 1 && ENC_REBASE_WINDOW == 64, "lzo1x_enc_rebase.h");
 constexpr uint32_t kMaxN = 1u << 24;            // larger blocks: the general encoder
 #ifndef POM_ENC_TOK
-#define POM_ENC_TOK 64
+#define POM_ENC_TOK 128                         // (64 until the grouped kernel: its queues absorb the emit wave's latency)
 #endif
 #ifndef POM_ENC_CLAIM
 #define POM_ENC_CLAIM 1024
@@ -342,14 +343,13 @@ struct Emitter {
     uint32_t ct;                                     // tokens consumed
     uint32_t pos;                                    // input covered by the tokens so far
     bool poisoned;                                   // a token the parse cannot have meant
-    bool prio;                                       // (one-wave kernel) wave priority by input left
     uint32_t* olen;                                  // out_len / status / block of drain(prod)
     int32_t* ost;
     uint32_t blk;
 
     __device__ __forceinline__ Emitter(EncLdsT<GD>& S_, const uint8_t* in, uint32_t n_, uint8_t* out,
                                        uint32_t cap)
-        : S(S_), B(block_src(in, n_)), n(n_), ct(0), pos(0), poisoned(false), prio(false), olen(nullptr),
+        : S(S_), B(block_src(in, n_)), n(n_), ct(0), pos(0), poisoned(false), olen(nullptr),
           ost(nullptr), blk(0)
     {
         e.in = in;
@@ -527,10 +527,12 @@ struct Emitter {
 // forwarding rounds after it.  EC_FALSE: flagged lanes with no writer.
 // EC_HWID, EC_XCC (one-wave kernel): the HW_ID and XCC_ID registers of the
 // wave that ran the block -- which CU of which XCD.  EP_REBASE, EC_REBASE:
-// the dictionary re-bases (none in a block of up to 65,548 bytes).
+// the dictionary re-bases (none in a block of up to 65,548 bytes).  EC_T0,
+// EC_T1 (one-wave and grouped kernels): s_memtime when the wave took the block
+// and when it had pushed its tail -- which blocks of a launch ran side by side.
 enum { EP_SETUP, EP_PROBE, EP_CAND, EP_PATH, EP_CLAIM, EP_TOK, EP_DICT, EP_PUSHWAIT,
        EC_WINDOWS, EC_EXTEND, EC_TOKENS, EC_PATHIT, EC_EXTIT, EC_C2NEED, EC_C2MATCH, EC_FWD,
-       EP_FWDR, EC_FALSE, EC_HWID, EC_XCC, EP_REBASE, EC_REBASE, EP_N };
+       EP_FWDR, EC_FALSE, EC_HWID, EC_XCC, EP_REBASE, EC_REBASE, EC_T0, EC_T1, EP_N };
 constexpr int kEncStampSlots = 24;
 static_assert(EP_N <= kEncStampSlots, "stamp slots");
 
@@ -541,10 +543,19 @@ static_assert(EP_N <= kEncStampSlots, "stamp slots");
 #ifndef POM_ENC_DRAIN
 #define POM_ENC_DRAIN 48
 #endif
-template <bool STAMPS, bool GD, bool FUSED = false>
+// GROUP (grouped kernel): the tokens go to an emit wave that several parse
+// waves share (enc_group_body).  The wave is scheduled like the one-wave
+// kernel's -- 16 blocks a CU -- so it takes that kernel's choices where the
+// two-wave kernels differ: priority by input left (prio), the next window's
+// probe words issued early, and no S.ip for a read-ahead.  It re-bases with 4
+// loads in flight like the two-wave kernels: 8 cost 24 VGPRs more, and the
+// wave has to fit 80 or 64 (POM_ENC_GROUP_OCC).
+template <bool STAMPS, bool GD, bool FUSED = false, bool GROUP = false>
 __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, uint32_t n, uint32_t l,
-                           uint64_t* acc, Emitter<GD>* E = nullptr)
+                           uint64_t* acc, Emitter<GD>* E = nullptr, bool prio = false)
 {
+    static_assert(!(FUSED && GROUP), "the parse wave emits, or an emit wave does");
+    constexpr bool ONE = FUSED || GROUP;            // scheduled as the one-wave kernel is
     uint64_t tmark = STAMPS ? __builtin_amdgcn_s_memtime() : 0;
 #define ESTAMP(ph)                                                  \
     do {                                                            \
@@ -597,8 +608,8 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
         uint32_t ip = 4;
         uint32_t base = 0;                          // dictionary position base
         uint32_t wtag = 0xFFFFFEu;                  // claim tag of the window (one per window, > 0)
-        // (FUSED priority) next ip at which it steps down; never without priority
-        uint32_t prio_ip = FUSED && E->prio ? 0u : 0xFFFFFFFFu;
+        // (priority) next ip at which it steps down; never without priority
+        uint32_t prio_ip = ONE && prio ? 0u : 0xFFFFFFFFu;
         // Probe words of the window (position ip + l): the next window's are
         // read as soon as its start is known, ahead of the token and
         // dictionary writes.
@@ -608,11 +619,11 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
         for (;;) {
             if (STAMPS)
                 acc[EC_WINDOWS] += 1;
-            // (one-wave kernel, one block per workgroup) blocks that are behind
+            // (one-wave and grouped kernels, one block per wave) blocks that are behind
             // (more input left) get the issue slots first, so the workgroups of
             // a CU finish together.  The priority steps down at most three
             // times a block: it is set again only once ip passes prio_ip.
-            if (FUSED && ip >= prio_ip) {
+            if (ONE && ip >= prio_ip) {
                 const uint32_t left = n - ip, st = POM_ENC_PRIO_STEP;
                 const uint32_t q = __builtin_amdgcn_readfirstlane(left >= 3u * st ? 3u : left >= 2u * st ? 2u
                                                                   : left >= st ? 1u : 0u);
@@ -629,7 +640,8 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                 ESTAMP(EP_DICT);
                 // (in flight per lane: 8 x 16 bytes in the one-wave kernel; 4 in
                 // the two-wave ones, which are capped at 64 VGPRs and spill --
-                // no more with 4 than without)
+                // no more with 4 than without, DESIGN.md §3.3 -- and in the
+                // grouped one)
                 rebase_dict<GD, FUSED ? 8 : 4>(D, nb - base, l);
                 wave_order();
                 base = nb;
@@ -637,7 +649,7 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                     acc[EC_REBASE] += 1;
                 ESTAMP(EP_REBASE);
             }
-            if (!FUSED && POM_ENC_AHEAD)
+            if (!ONE && POM_ENC_AHEAD)
                 S.ip = ip;                          // (the emit wave reads ahead from here)
             const uint32_t p = ip + l;
             const bool active = l == 0 || p < ip_end;   // the first probe always runs
@@ -766,7 +778,7 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
             // re-walks' extension loads behind it (lone 64 KiB 655 -> 675 us).
             uint32_t npw[kCmpW];
             const uint32_t end0 = end;
-            if (FUSED)
+            if (ONE)
                 load_at<kCmpW>(B, ip + end0 + l, npw);
             ESTAMP(EP_PATH);
             // ---- exactness: fixed per-lane flags, and forwarding ---------------
@@ -858,7 +870,7 @@ __device__ void parse_wave(EncLdsT<GD>& S, const Dict<GD> D, const uint8_t* in, 
                 acc[EC_C2MATCH] += nmatch >= POM_ENC_PATHMAX ? 1 : 0;   // the path cap
             }
             const uint64_t keep = end >= 64 ? ~0ull : ((1ull << end) - 1);
-            if (!FUSED || end != end0)
+            if (!ONE || end != end0)
                 load_at<kCmpW>(B, ip + end + l, npw);
 
             ESTAMP(EP_FWDR);
@@ -1110,12 +1122,15 @@ __device__ __forceinline__ void gdict1_body(
         E.olen = out_len;
         E.ost = status;
         E.blk = b;
-        E.prio = !dyn;                               // (block tickets: mixed sizes, no priority)
         uint64_t acc[EP_N] = {};
-        parse_wave<STAMPS, true, true>(S, D, in, n, l, acc, &E);
+        const uint64_t t0 = STAMPS ? __builtin_amdgcn_s_memtime() : 0;
+        // (block tickets: mixed sizes, no priority)
+        parse_wave<STAMPS, true, true>(S, D, in, n, l, acc, &E, !dyn);
         if (STAMPS) {                                // (s_getreg_b32 of HW_REG_HW_ID and HW_REG_XCC_ID, all 32 bits)
             acc[EC_HWID] = __builtin_amdgcn_s_getreg(4 | (31 << 11));
             acc[EC_XCC] = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+            acc[EC_T0] = t0;
+            acc[EC_T1] = __builtin_amdgcn_s_memtime();
         }
         if (STAMPS && l == 0)
             for (int i = 0; i < EP_N; i++)
@@ -1124,7 +1139,10 @@ __device__ __forceinline__ void gdict1_body(
     }
 }
 
-__global__ __launch_bounds__(kWave, POM_ENC_RESIDENT1 / 4) void lzo1x_encode_gdict1_kernel(
+// (gdict1f: the one-wave kernel with the emitter fused into the parse wave.
+// It runs the batches the grouped kernel below leaves to it, enc_group_use,
+// and everything under the debug key enc_waves=1.)
+__global__ __launch_bounds__(kWave, POM_ENC_RESIDENT1 / 4) void lzo1x_encode_gdict1f_kernel(
     const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
     const uint32_t* __restrict__ src_len, uint8_t* __restrict__ dst,
     const uint64_t* __restrict__ dst_off, const uint32_t* __restrict__ dst_cap,
@@ -1136,7 +1154,7 @@ __global__ __launch_bounds__(kWave, POM_ENC_RESIDENT1 / 4) void lzo1x_encode_gdi
 }
 
 // (diagnostic) the same with the parse wave's phase stamps
-__global__ __launch_bounds__(kWave, POM_ENC_RESIDENT1 / 4) void lzo1x_encode_gdict1_stamps_kernel(
+__global__ __launch_bounds__(kWave, POM_ENC_RESIDENT1 / 4) void lzo1x_encode_gdict1f_stamps_kernel(
     const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
     const uint32_t* __restrict__ src_len, uint8_t* __restrict__ dst,
     const uint64_t* __restrict__ dst_off, const uint32_t* __restrict__ dst_cap,
@@ -1147,29 +1165,407 @@ __global__ __launch_bounds__(kWave, POM_ENC_RESIDENT1 / 4) void lzo1x_encode_gdi
                       nullptr, stamps);
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------
+// Grouped global-dictionary encoder: one block per parse wave as in the
+// one-wave kernel, but G parse waves to a workgroup and E emit waves that
+// serve their token queues (lzo1x_enc_group.h: who owns which region and
+// slot).  The parse waves only parse (parse_wave<.., GROUP>): emission -- the
+// queue reads, two wave scans, the literal loads, the ring writes and the
+// flush to HBM -- is off every block's chain and out of the parse wave's
+// in-order load queue, while a CU still holds 16 blocks at 96 VGPRs a wave
+// or less (2 workgroups of 8 + 2 waves; POM_ENC_GROUP_OCC below).  The waves
+// of a workgroup run independently; there is no barrier after the control
+// records are set up.
+// ---------------------------------------------------------------------------
+#ifndef POM_ENC_GROUP
+#define POM_ENC_GROUP 8                         // parse waves per workgroup (the default shape)
+#endif
+#ifndef POM_ENC_EMITTERS
+#define POM_ENC_EMITTERS 2                      // emit waves per workgroup
+#endif
+#ifndef POM_ENC_GDRAIN
+#define POM_ENC_GDRAIN POM_ENC_DRAIN            // pending tokens from which the emit wave drains a slot
+#endif
+#ifndef POM_ENC_EMIT_PRIO
+#define POM_ENC_EMIT_PRIO 0                     // the emit wave's priority (parse waves: 3 .. 0 by input left)
+#endif
+// A parse wave waits for room only with more than kTok - POM_ENC_PATHMAX
+// tokens pending: the emit wave must take such a queue.
+static_assert(POM_ENC_GDRAIN + POM_ENC_PATHMAX <= kTok + 1, "a full queue qualifies for a drain");
 
-// Waves per block of the global-dictionary encoder: debug key enc_waves of
-// POM_LZO_DEBUG (1 or 2, read at every launch, for the tests of both
-// kernels), default 1.
-static int enc_waves(void)
+// Control record of a parse slot.  gen, tail and exit are written by the
+// parse wave, fin by the emit wave, each with a release store after what it
+// publishes; the block's parameters and the emitter state are written by the
+// parse wave at the hand-over (before gen) and between gen and fin belong to
+// the emit wave.
+struct GroupSlot {
+    const uint8_t* in;
+    uint8_t* out;
+    uint32_t n, cap, b;
+    uint32_t gen;                   // blocks handed to the emit wave
+    uint32_t fin;                   // blocks whose out_len and status are written
+    uint32_t tail;                  // the block's tail token is in the queue
+    uint32_t exit;                  // the parse wave takes no more blocks
+    uint32_t ct, pos, op, flushed, poisoned;    // Emitter state between two drains
+};
+template <int G>
+struct GroupLds {
+    EncLdsT<true> S[G];
+    GroupSlot C[G];
+};
+static_assert(sizeof(GroupLds<4>) * (POM_ENC_RESIDENT1 / 4) <= 160 * 1024, "four workgroups of 4 + 1 per CU");
+static_assert(sizeof(GroupLds<8>) * (POM_ENC_RESIDENT1 / 8) <= 160 * 1024, "two workgroups of 8 + E per CU");
+
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+template <typename T>
+__device__ __forceinline__ T* uniform_ptr(T* p)
 {
-    return pom_dbg_int("enc_waves", 1) == 2 ? 2 : 1;
+    const uintptr_t a = (uintptr_t)p;
+    return (T*)(((uintptr_t)uniform((uint32_t)(a >> 32)) << 32) | uniform((uint32_t)a));
 }
 
-static uint32_t enc_resident(void)
+template <bool STAMPS, int G>
+__device__ __forceinline__ void group_parse(
+    GroupLds<G>& L, uint32_t w, const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
+    const uint32_t* __restrict__ src_len, uint8_t* __restrict__ dst,
+    const uint64_t* __restrict__ dst_off, const uint32_t* __restrict__ dst_cap,
+    int32_t* __restrict__ status, uint32_t nblocks, uint8_t* __restrict__ dicts, uint32_t regions,
+    const uint32_t* __restrict__ order, uint64_t* __restrict__ stamps)
+{
+    EncLdsT<true>& S = L.S[w];
+    GroupSlot& C = L.C[w];
+    const uint32_t l = lane_id();
+    if (!enc_group_idle(blockIdx.x, w, G, regions)) {
+        const uint32_t region = enc_group_region(blockIdx.x, w, G);
+        Dict<true> D;
+        D.lds = nullptr;
+        D.g = (gu16*)(dicts + kScratchHead + (size_t)region * kDictBytes);
+        D.occ = S.occ;
+        D.rs = __builtin_amdgcn_make_buffer_rsrc((void*)D.g, 0, (int)(kSlots * 2), 0x00020000);
+        const bool dyn = nblocks > regions;         // block tickets, as next_block: region r starts with block r
+        uint32_t gen = 0;
+        for (uint32_t t = region; t < nblocks;) {
+            const uint32_t b = order ? order[t] : t; // (largest first: lzo_mi355x_launch_order_by_size)
+            const uint32_t n = src_len[b];
+            if (n > kMaxN) {                         // the general encoder's
+                if (l == 0)
+                    status[b] = LZO_MI355X_ENC_PENDING;
+            } else {
+                const uint8_t* in = src + src_off[b];
+                // Hand-over.  The slot's previous block must be out (fin ==
+                // gen) before its queue and control record are reused.
+                // Progress: this wave pushed that block's tail token before it
+                // came here, so the emit wave has everything it needs to
+                // finish it, and the emit wave never waits for a parse wave
+                // that waits: it only sleeps while NO slot of its own has
+                // tokens to drain, and a slot whose tail is pushed always has.
+                // The other wait of a parse wave, for queue room (parse_wave's
+                // push), is for a queue with more than kTok - POM_ENC_PATHMAX
+                // tokens pending, which qualifies for a drain by the
+                // static_assert above.  So every wait is for the emit wave,
+                // the emit wave's only wait is for a parse wave that is
+                // parsing, not waiting, and parsing ends.
+                while (uniform(lds_load(&C.fin)) != gen)
+                    __builtin_amdgcn_s_sleep(POM_EMIT_SLEEP);
+                if (l == 0) {
+                    C.in = in;
+                    C.out = dst + dst_off[b];
+                    C.n = n;
+                    C.cap = dst_cap[b];
+                    C.b = b;
+                    C.tail = 0;
+                    C.ct = C.pos = C.op = C.flushed = C.poisoned = 0;
+                    S.prod = 0;
+                    S.cons = 0;
+                }
+                wave_order();
+                gen++;
+                lds_store(&C.gen, gen);              // (release: the emit wave picks the block up on an acquire load)
+                uint64_t acc[EP_N] = {};
+                const uint64_t t0 = STAMPS ? __builtin_amdgcn_s_memtime() : 0;
+                parse_wave<STAMPS, true, false, true>(S, D, in, n, l, acc, nullptr, !dyn);
+                lds_store(&C.tail, 1u);              // (after the tail token's S.prod)
+                if (STAMPS) {                        // (s_getreg_b32 of HW_REG_HW_ID and HW_REG_XCC_ID, all 32 bits)
+                    acc[EC_HWID] = __builtin_amdgcn_s_getreg(4 | (31 << 11));
+                    acc[EC_XCC] = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+                    acc[EC_T0] = t0;
+                    acc[EC_T1] = __builtin_amdgcn_s_memtime();
+                }
+                if (STAMPS && l == 0)
+                    for (int i = 0; i < EP_N; i++)
+                        stamps[(size_t)b * kEncStampSlots + i] = acc[i];
+            }
+            if (!dyn)
+                break;
+            uint32_t tk = 0;
+            if (l == 0)
+                tk = atomicAdd((uint32_t*)dicts, 1u);
+            t = regions + uniform(tk);
+        }
+    }
+    lds_store(&C.exit, 1u);
+}
+
+// Emit wave e: drains, of its slots, the one with the fullest queue among
+// those with POM_ENC_GDRAIN tokens pending or the tail token pushed; sleeps
+// when none qualifies; returns when all have reported exit and are drained.
+// The Emitter of a slot is rebuilt from its control record for every drain
+// and its state put back, so nothing of it is indexed by slot in registers.
+template <int G, int E>
+__device__ __forceinline__ void group_emit(GroupLds<G>& L, uint32_t e, uint32_t* __restrict__ out_len,
+                                           int32_t* __restrict__ status)
+{
+    switch (POM_ENC_EMIT_PRIO) {
+    case 3: __builtin_amdgcn_s_setprio(3); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    default: break;
+    }
+    const uint32_t s0 = enc_group_emit_first(e, G, E), s1 = s0 + enc_group_emit_count(e, G, E);
+    const uint32_t l = lane_id();
+    for (;;) {
+        uint32_t best = s1, best_pend = 0, best_prod = 0, best_gen = 0;
+        bool all_out = true;
+        for (uint32_t s = s0; s < s1; s++) {
+            GroupSlot& C = L.C[s];
+            // (exit before gen: a slot is out for good when it reported exit
+            // and no block was handed over before that)
+            const uint32_t ex = uniform(lds_load(&C.exit));
+            const uint32_t gen = uniform(lds_load(&C.gen));
+            if (gen == uniform(lds_load(&C.fin))) {
+                all_out = all_out && ex != 0;
+                continue;
+            }
+            all_out = false;
+            const uint32_t tail = uniform(lds_load(&C.tail));       // (before prod: then prod is final)
+            const uint32_t prod = uniform(lds_load(&L.S[s].prod));
+            const uint32_t pend = prod - uniform(C.ct);
+            if ((pend >= (uint32_t)POM_ENC_GDRAIN || (tail && pend)) && pend > best_pend) {
+                best = s;
+                best_pend = pend;
+                best_prod = prod;
+                best_gen = gen;
+            }
+        }
+        if (best == s1) {
+            if (all_out)
+                return;
+            __builtin_amdgcn_s_sleep(POM_EMIT_SLEEP);
+            continue;
+        }
+        GroupSlot& C = L.C[best];
+        Emitter<true> Em(L.S[best], uniform_ptr(C.in), uniform(C.n), uniform_ptr(C.out), uniform(C.cap));
+        Em.ct = uniform(C.ct);
+        Em.pos = uniform(C.pos);
+        Em.e.op = uniform(C.op);
+        Em.e.flushed = uniform(C.flushed);
+        Em.poisoned = uniform(C.poisoned) != 0;
+        const bool done = Em.drain(best_prod, out_len, status, uniform(C.b));
+        if (l == 0) {
+            C.ct = Em.ct;
+            C.pos = Em.pos;
+            C.op = Em.e.op;
+            C.flushed = Em.e.flushed;
+            C.poisoned = Em.poisoned ? 1u : 0u;
+        }
+        wave_order();
+        if (done)
+            lds_store(&C.fin, best_gen);             // (release: the slot may take its next block)
+    }
+}
+
+template <bool STAMPS, int G, int E>
+__device__ __forceinline__ void enc_group_body(
+    const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
+    const uint32_t* __restrict__ src_len, uint8_t* __restrict__ dst,
+    const uint64_t* __restrict__ dst_off, const uint32_t* __restrict__ dst_cap,
+    uint32_t* __restrict__ out_len, int32_t* __restrict__ status, uint32_t nblocks,
+    uint8_t* __restrict__ dicts, uint32_t regions, const uint32_t* __restrict__ order,
+    uint64_t* __restrict__ stamps)
+{
+    static_assert(G % E == 0, "every emit wave serves as many slots");
+    // (dynamic LDS, sizeof(GroupLds<G>) at the launch: with a static size the
+    // compiler derives the occupancy from it and will not hold the registers
+    // to what POM_ENC_GROUP_OCC asks for)
+    extern __shared__ __attribute__((aligned(16))) uint8_t enc_group_lds[];
+    GroupLds<G>& L = *(GroupLds<G>*)enc_group_lds;
+    if (threadIdx.x < G) {
+        GroupSlot& C = L.C[threadIdx.x];
+        C.gen = C.fin = C.tail = C.exit = 0;
+        C.ct = 0;
+    }
+    __syncthreads();                                 // (the only barrier: the control records are set up)
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    if (wave < G)
+        group_parse<STAMPS, G>(L, wave, src, src_off, src_len, dst, dst_off, dst_cap, status, nblocks, dicts,
+                               regions, order, stamps);
+    else
+        group_emit<G, E>(L, wave - G, out_len, status);
+}
+
+#define POM_ENC_GROUP_ARGS                                                                         \
+    const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,                        \
+        const uint32_t *__restrict__ src_len, uint8_t *__restrict__ dst,                          \
+        const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ dst_cap,               \
+        uint32_t *__restrict__ out_len, int32_t *__restrict__ status, uint32_t nblocks,           \
+        uint8_t *__restrict__ dicts, uint32_t regions, const uint32_t *__restrict__ order,        \
+        uint64_t *__restrict__ stamps
+#define POM_ENC_GROUP_PASS \
+    src, src_off, src_len, dst, dst_off, dst_cap, out_len, status, nblocks, dicts, regions, order, stamps
+// Waves per SIMD the registers must leave room for.  The waves of a workgroup
+// go to the SIMDs in turn from the first one (measured, DESIGN.md 3.3: built
+// for five waves a SIMD, 96 VGPRs, every shape ran with 8 blocks a CU
+// resident, not 16, and took 2.1 ms instead of 1.4), so the first SIMD holds
+// ceil((G + E) / 4) waves of each of the CU's 16 / G workgroups: 6 for 8 + 1,
+// 8 + 2 and 8 + 4 (80 VGPRs), 8 for 4 + 1 (64).  The grouped parse wave needs
+// 66 (it re-bases with 4 loads in flight, not 8) and fits 64 without a spill.
+// (POM_ENC_GROUP_EU: another figure, for the A/B runs of the register budget)
+#ifdef POM_ENC_GROUP_EU
+#define POM_ENC_GROUP_OCC(G, E) POM_ENC_GROUP_EU
+#else
+#define POM_ENC_GROUP_OCC(G, E) (POM_ENC_RESIDENT1 / (G) * (((G) + (E) + 3) / 4))
+#endif
+#define POM_ENC_SHAPE (10 * POM_ENC_GROUP + POM_ENC_EMITTERS)
+static_assert(POM_ENC_SHAPE == 41 || POM_ENC_SHAPE == 81 || POM_ENC_SHAPE == 82 || POM_ENC_SHAPE == 84,
+              "a shape the launcher knows");
+
+// The default encoder of device batches with scratch, in the default shape.
+__global__ __launch_bounds__((POM_ENC_GROUP + POM_ENC_EMITTERS) * kWave,
+                             POM_ENC_GROUP_OCC(POM_ENC_GROUP, POM_ENC_EMITTERS))
+void lzo1x_encode_gdict1_kernel(POM_ENC_GROUP_ARGS)
+{
+    enc_group_body<false, POM_ENC_GROUP, POM_ENC_EMITTERS>(POM_ENC_GROUP_PASS);
+}
+
+// (diagnostic) the same with the parse waves' phase stamps
+__global__ __launch_bounds__((POM_ENC_GROUP + POM_ENC_EMITTERS) * kWave,
+                             POM_ENC_GROUP_OCC(POM_ENC_GROUP, POM_ENC_EMITTERS))
+void lzo1x_encode_gdict1_stamps_kernel(POM_ENC_GROUP_ARGS)
+{
+    enc_group_body<true, POM_ENC_GROUP, POM_ENC_EMITTERS>(POM_ENC_GROUP_PASS);
+}
+
+// (debug key enc_group=41 / 81 / 82 / 84) the other shapes
+#define POM_ENC_GROUP_KERNEL(name, G, E)                                                            \
+    __global__ __launch_bounds__(((G) + (E)) * kWave, POM_ENC_GROUP_OCC(G, E)) void name(POM_ENC_GROUP_ARGS) \
+    {                                                                                               \
+        enc_group_body<false, G, E>(POM_ENC_GROUP_PASS);                                            \
+    }
+#if POM_ENC_SHAPE != 41
+POM_ENC_GROUP_KERNEL(lzo1x_encode_gdict1_g41_kernel, 4, 1)
+#endif
+#if POM_ENC_SHAPE != 81
+POM_ENC_GROUP_KERNEL(lzo1x_encode_gdict1_g81_kernel, 8, 1)
+#endif
+#if POM_ENC_SHAPE != 82
+POM_ENC_GROUP_KERNEL(lzo1x_encode_gdict1_g82_kernel, 8, 2)
+#endif
+#if POM_ENC_SHAPE != 84
+POM_ENC_GROUP_KERNEL(lzo1x_encode_gdict1_g84_kernel, 8, 4)
+#endif
+
+}  // namespace
+
+// Which encoder a device batch takes.  Debug keys of POM_LZO_DEBUG, read at
+// every launch (the tests and A/B runs of each kernel): enc_waves=1 the
+// one-wave kernel (lzo1x_encode_gdict1f_kernel), enc_waves=2 the two-wave one;
+// otherwise enc_group=41, 81, 82 or 84 the grouped kernel in that shape whatever
+// the batch; otherwise the rule of lzo1x_enc_group.h: the grouped kernel in
+// the default shape when enc_group_use says so, else the one-wave kernel.
+enum { ENC_K_LDS = 0, ENC_K_ONE = 1, ENC_K_TWO = 2, ENC_K_GROUP = POM_ENC_SHAPE };
+
+static int enc_waves(void)
+{
+    const long w = pom_dbg_int("enc_waves", 0);
+    return w == 1 || w == 2 ? (int)w : 0;
+}
+
+static uint32_t enc_cus(void);
+
+// The grouped kernel of `shape` (10 G + E): ceil(regions / G) workgroups of
+// G + E waves, sizeof(GroupLds<G>) bytes of LDS each.
+template <int G, typename K>
+static int enc_group_launch_shape(K kernel, int E, const uint8_t* src, const uint64_t* src_off,
+                                  const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                  const uint32_t* dst_cap, uint32_t* out_len, int32_t* status, uint32_t nblocks,
+                                  uint8_t* scratch, uint32_t regions, const uint32_t* order, uint64_t* stamps,
+                                  hipStream_t stream)
+{
+    const size_t lds = sizeof(GroupLds<G>);
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL(kernel, dim3(enc_group_workgroups(regions, G)), dim3((G + E) * kWave), lds, stream, src,
+                       src_off, src_len, dst, dst_off, dst_cap, out_len, status, nblocks, scratch, regions, order,
+                       stamps);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+static int enc_group_launch(int shape, bool stamps_build, const uint8_t* src, const uint64_t* src_off,
+                            const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                            const uint32_t* dst_cap, uint32_t* out_len, int32_t* status, uint32_t nblocks,
+                            uint8_t* scratch, uint32_t regions, const uint32_t* order, uint64_t* stamps,
+                            hipStream_t stream)
+{
+#define POM_ENC_GROUP_REST \
+    src, src_off, src_len, dst, dst_off, dst_cap, out_len, status, nblocks, scratch, regions, order, stamps, stream
+    if (stamps_build)
+        return enc_group_launch_shape<POM_ENC_GROUP>(lzo1x_encode_gdict1_stamps_kernel, POM_ENC_EMITTERS,
+                                                     POM_ENC_GROUP_REST);
+    if (shape == POM_ENC_SHAPE)
+        return enc_group_launch_shape<POM_ENC_GROUP>(lzo1x_encode_gdict1_kernel, POM_ENC_EMITTERS,
+                                                     POM_ENC_GROUP_REST);
+#if POM_ENC_SHAPE != 41
+    if (shape == 41)
+        return enc_group_launch_shape<4>(lzo1x_encode_gdict1_g41_kernel, 1, POM_ENC_GROUP_REST);
+#endif
+#if POM_ENC_SHAPE != 81
+    if (shape == 81)
+        return enc_group_launch_shape<8>(lzo1x_encode_gdict1_g81_kernel, 1, POM_ENC_GROUP_REST);
+#endif
+#if POM_ENC_SHAPE != 82
+    if (shape == 82)
+        return enc_group_launch_shape<8>(lzo1x_encode_gdict1_g82_kernel, 2, POM_ENC_GROUP_REST);
+#endif
+#if POM_ENC_SHAPE != 84
+    if (shape == 84)
+        return enc_group_launch_shape<8>(lzo1x_encode_gdict1_g84_kernel, 4, POM_ENC_GROUP_REST);
+#endif
+#undef POM_ENC_GROUP_REST
+    return -1;
+}
+
+// grid: the dictionary regions of the launch (0: no scratch, the LDS kernel)
+static int enc_kernel(uint32_t grid)
+{
+    if (!grid)
+        return ENC_K_LDS;
+    if (enc_waves())
+        return enc_waves();
+    const long g = pom_dbg_int("enc_group", 0);
+    if (g == 41 || g == 81 || g == 82 || g == 84)
+        return (int)g;
+    return enc_group_use(grid, POM_ENC_GROUP, enc_cus()) ? ENC_K_GROUP : ENC_K_ONE;
+}
+
+static uint32_t enc_cus(void)
 {
     static int cus[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-        return 256 * POM_ENC_RESIDENT;
+        return 256;
     if (!cus[dev]) {
         int n = 0;
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
             n = 256;
         cus[dev] = n;
     }
-    return (uint32_t)cus[dev] * (enc_waves() == 1 ? POM_ENC_RESIDENT1 : POM_ENC_RESIDENT);
+    return (uint32_t)cus[dev];
+}
+
+static uint32_t enc_resident(void)
+{
+    return enc_cus() * (enc_waves() == 2 ? POM_ENC_RESIDENT : POM_ENC_RESIDENT1);
 }
 
 // Start order of a batch with more blocks than resident workgroups (bytes at
@@ -1218,10 +1614,14 @@ extern "C" int lzo_mi355x_launch_compress_fast(const uint8_t* src, const uint64_
     const size_t order_at = kScratchHead + (size_t)grid * kDictBytes;
     uint32_t* order = grid && grid < nblocks && ob && order_at + ob <= scratch_bytes
                           ? (uint32_t*)((uint8_t*)scratch + order_at) : nullptr;
-    if (order && enc_waves() == 1 && lzo_mi355x_launch_order_by_size(src_len, nblocks, order, stream) != 0)
+    const int k = enc_kernel(grid);
+    if (order && k != ENC_K_TWO && lzo_mi355x_launch_order_by_size(src_len, nblocks, order, stream) != 0)
         return -1;
-    if (grid && enc_waves() == 1)
-        hipLaunchKernelGGL(lzo1x_encode_gdict1_kernel, dim3(grid), dim3(kWave), 0, stream, src, src_off,
+    if (k == 41 || k == 81 || k == 82 || k == 84)
+        return enc_group_launch(k, /*stamps=*/false, src, src_off, src_len, dst, dst_off, dst_cap, out_len, status,
+                                nblocks, (uint8_t*)scratch, grid, order, nullptr, stream);
+    if (k == ENC_K_ONE)
+        hipLaunchKernelGGL(lzo1x_encode_gdict1f_kernel, dim3(grid), dim3(kWave), 0, stream, src, src_off,
                            src_len, dst, dst_off, dst_cap, out_len, status, nblocks, (uint8_t*)scratch,
                            (const uint32_t*)order);
     else if (grid)
@@ -1269,7 +1669,7 @@ extern "C" int lzo_mi355x_debug_compress_gdict_stamps(const uint8_t* src, const 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// Diagnostic: the one-wave global-dictionary encoder (the bench's) with
+// Diagnostic: the one-wave global-dictionary encoder with
 // parse-wave phase stamps (24 x u64 per block; no start order).
 extern "C" int lzo_mi355x_debug_compress_gdict1_stamps(const uint8_t* src, const uint64_t* src_off,
                                                        const uint32_t* src_len, uint8_t* dst,
@@ -1282,8 +1682,34 @@ extern "C" int lzo_mi355x_debug_compress_gdict1_stamps(const uint8_t* src, const
     const uint32_t grid = enc_grid(scratch_bytes, nblocks);
     if (grid == 0 || (grid < nblocks && hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream) != hipSuccess))
         return -1;
-    hipLaunchKernelGGL(lzo1x_encode_gdict1_stamps_kernel, dim3(grid), dim3(kWave), 0, stream,
+    hipLaunchKernelGGL(lzo1x_encode_gdict1f_stamps_kernel, dim3(grid), dim3(kWave), 0, stream,
                        src, src_off, src_len, dst, dst_off, dst_cap, out_len, status, nblocks,
                        (uint8_t*)scratch, stamps);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Diagnostic: the grouped global-dictionary encoder (the bench's) in its
+// default shape with the parse waves' phase stamps (24 x u64 per block; no
+// start order).
+extern "C" int lzo_mi355x_debug_compress_group_stamps(const uint8_t* src, const uint64_t* src_off,
+                                                      const uint32_t* src_len, uint8_t* dst,
+                                                      const uint64_t* dst_off,
+                                                      const uint32_t* dst_cap, uint32_t* out_len,
+                                                      int32_t* status, uint32_t nblocks,
+                                                      void* scratch, size_t scratch_bytes,
+                                                      uint64_t* stamps, hipStream_t stream)
+{
+    const uint32_t grid = enc_grid(scratch_bytes, nblocks);
+    if (grid == 0 || (grid < nblocks && hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream) != hipSuccess))
+        return -1;
+    return enc_group_launch(POM_ENC_SHAPE, /*stamps=*/true, src, src_off, src_len, dst, dst_off, dst_cap, out_len,
+                            status, nblocks, (uint8_t*)scratch, grid, nullptr, stamps, stream);
+}
+
+// Diagnostic: the encoder lzo_mi355x_launch_compress_fast would run on such a
+// batch: 0 the LDS-dictionary kernel, 1 the one-wave and 2 the two-wave
+// global-dictionary kernel, 10 G + E the grouped one in the shape G + E.
+extern "C" int lzo_mi355x_debug_enc_kernel(uint32_t nblocks, int have_scratch, size_t scratch_bytes)
+{
+    return nblocks ? enc_kernel(have_scratch ? enc_grid(scratch_bytes, nblocks) : 0u) : 0;
 }

@@ -43,15 +43,22 @@ g1fn = getattr(lib, "lzo_mi355x_debug_compress_gdict1_stamps", None)
 if g1fn is not None:
     g1fn.restype = ctypes.c_int
     g1fn.argtypes = gfn.argtypes
+grfn = getattr(lib, "lzo_mi355x_debug_compress_group_stamps", None)   # (the bench's grouped kernel)
+if grfn is not None:
+    grfn.restype = ctypes.c_int
+    grfn.argtypes = gfn.argtypes
 p = lambda x: x.data_ptr()
 sh = torch.cuda.current_stream().cuda_stream
 scr = torch.empty(max(lzo.compress_scratch_bytes(nb), 1), dtype=torch.uint8, device=dev)
 ref_out = None
 gstamps = torch.zeros(nb * SLOTS, dtype=torch.int64, device=dev)
 g1stamps = torch.zeros(nb * SLOTS, dtype=torch.int64, device=dev)
-STAMPED = ("stamps", "gstamps", "g1stamps")
-for mode in ("lds", "gdict", "stamps", "gstamps", "g1stamps"):
+grstamps = torch.zeros(nb * SLOTS, dtype=torch.int64, device=dev)
+STAMPED = ("stamps", "gstamps", "g1stamps", "grstamps")
+for mode in ("lds", "gdict", "stamps", "gstamps", "g1stamps", "grstamps"):
     if mode in STAMPED and (fn is None or gfn is None or g1fn is None or a.nostamps):
+        continue
+    if mode == "grstamps" and grfn is None:
         continue
     ts = []
     for _ in range(1 if mode in STAMPED else 5):
@@ -63,7 +70,10 @@ for mode in ("lds", "gdict", "stamps", "gstamps", "g1stamps"):
         elif mode == "gstamps":
             gfn(p(src.arena), p(src.off), p(src.length), p(za), p(zb.off), p(zb.length), p(zl), p(zs), nb,
                 p(scr), scr.numel(), p(gstamps), sh)
-        elif mode == "g1stamps":               # (the bench's one-wave kernel)
+        elif mode == "grstamps":               # (the bench's grouped kernel)
+            grfn(p(src.arena), p(src.off), p(src.length), p(za), p(zb.off), p(zb.length), p(zl), p(zs), nb,
+                 p(scr), scr.numel(), p(grstamps), sh)
+        elif mode == "g1stamps":               # (the one-wave kernel)
             g1fn(p(src.arena), p(src.off), p(src.length), p(za), p(zb.off), p(zb.length), p(zl), p(zs), nb,
                  p(scr), scr.numel(), p(g1stamps), sh)
         else:
@@ -86,8 +96,11 @@ counts = ["windows", "extend", "tokens", "pathit", "extit", "end_cross", "end_ca
 # to the first conflict mask --, false alarms, and the HW_ID and XCC_ID registers;
 # slots 20, 21: the dictionary re-bases' cycles and their count -- 0 per block
 # up to 65,548 bytes)
-FWDR, FALSE, HWID, XCC, REBASE, NREBASE = 16, 17, 18, 19, 20, 21
-for name, t_ in (("lds", stamps), ("gdict", gstamps), ("gdict1", g1stamps)):
+FWDR, FALSE, HWID, XCC, REBASE, NREBASE, T0, T1 = 16, 17, 18, 19, 20, 21, 22, 23
+runs = [("lds", stamps), ("gdict", gstamps), ("gdict1f", g1stamps)]
+if grfn is not None:
+    runs.append(("group", grstamps))
+for name, t_ in runs:
     st = t_.view(nb, SLOTS).double().cpu().numpy()
     cyc = {n: int(st[:, i].mean()) for i, n in enumerate(phases)}
     cyc["fwdrounds"] = int(st[:, FWDR].mean())
@@ -99,12 +112,25 @@ for name, t_ in (("lds", stamps), ("gdict", gstamps), ("gdict1", g1stamps)):
     cnt["false_alarm"] = round(float(st[:, FALSE].mean()), 1)
     cnt["rebase"] = round(float(st[:, NREBASE].mean()), 2)
     print(name, "counts/block (mean):", cnt)
-# Where the one-wave kernel's blocks ran: HW_ID has cu_id in bits 11:8, sh_id in
-# bit 12 and se_id in bits 15:13; XCC_ID has the XCD in bits 3:0.
-raw = g1stamps.view(nb, SLOTS).cpu().numpy()
-hw, xcc = raw[:, HWID], raw[:, XCC] & 0xF
-cu = (xcc << 8) | (((hw >> 13) & 7) << 5) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xF)
-per_cu = np.bincount(np.unique(cu, return_inverse=True)[1])
-print(f"gdict1 blocks per CU: {len(per_cu)} CUs used, histogram (blocks: CUs)",
-      {int(k): int(v) for k, v in zip(*np.unique(per_cu, return_counts=True))})
-print("gdict1 blocks per XCD:", {int(k): int(v) for k, v in zip(*np.unique(xcc, return_counts=True))})
+# Where and when the one-wave and grouped kernels' blocks ran: HW_ID has the
+# SIMD in bits 5:4, cu_id in bits 11:8, sh_id in bit 12 and se_id in bits
+# 15:13; XCC_ID has the XCD in bits 3:0.  T0 / T1: s_memtime (100 MHz) at the
+# block's start and after its tail token -- blocks that start late ran in a
+# second round, after others of their CU had ended.
+for name, t_ in runs[2:]:
+    raw = t_.view(nb, SLOTS).cpu().numpy()
+    hw, xcc = raw[:, HWID], raw[:, XCC] & 0xF
+    cu = (xcc << 8) | (((hw >> 13) & 7) << 5) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xF)
+    per_cu = np.bincount(np.unique(cu, return_inverse=True)[1])
+    print(f"{name} blocks per CU: {len(per_cu)} CUs used, histogram (blocks: CUs)",
+          {int(k): int(v) for k, v in zip(*np.unique(per_cu, return_counts=True))})
+    print(f"{name} blocks per XCD:", {int(k): int(v) for k, v in zip(*np.unique(xcc, return_counts=True))})
+    simd = (hw >> 4) & 3
+    per_simd = np.bincount((np.unique(cu, return_inverse=True)[1] << 2) | simd)
+    print(f"{name} blocks per SIMD of a CU, histogram (blocks: SIMDs)",
+          {int(k): int(v) for k, v in zip(*np.unique(per_simd, return_counts=True))})
+    t0 = (raw[:, T0] - raw[:, T0].min()) / 100.0          # us
+    dur = (raw[:, T1] - raw[:, T0]) / 100.0
+    print(f"{name} block start after the first (us): deciles",
+          [round(float(x), 1) for x in np.percentile(t0, range(0, 101, 10))])
+    print(f"{name} block duration (us): deciles", [round(float(x), 1) for x in np.percentile(dur, range(0, 101, 10))])
