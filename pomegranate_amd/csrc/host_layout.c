@@ -1,6 +1,7 @@
 /* host_layout.c -- the staging layouts of host_layout.h: plain arithmetic, no
  * HIP.  Each builder lays the arrays out in the order its operation's staging
- * diagram gives (lzo_host.c for the codec, host_records.c for the others). */
+ * diagram gives (lzo_host.c for the codec, host_single.c for the single calls,
+ * host_records.c for the others). */
 #include <string.h>
 
 #include "host_layout.h"
@@ -62,6 +63,32 @@ void pom_layout_codec(struct layout *L, const size_t *ids, size_t nb, const size
     L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
     L->u.codec.o_pack = take(&o, out);
     L->dtotal = o;
+}
+
+void pom_layout_single(struct single_layout *L, size_t k, const size_t *src_len, const size_t *room,
+                       size_t *o_src, size_t *o_out)
+{
+    size_t o = 0;
+    L->o_srcoff = take(&o, 8 * k);
+    L->o_dstoff = take(&o, 8 * k);
+    L->o_srclen = take(&o, 4 * k);
+    L->o_dstcap = take(&o, 4 * k);
+    L->o_outlen = take(&o, 4 * k);
+    L->o_status = take(&o, 4 * k);
+    L->pre_off = o;
+    L->o_plen = take(&o, 4 * k);
+    L->o_pstatus = take(&o, 4 * k);
+    L->pre_bytes = o - L->pre_off;
+    L->o_fb = take(&o, 4 * (1 + k));
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = o;
+    for (size_t i = 0; i < k; i++)
+        o_src[i] = take(&o, POM_ALIGN_UP(src_len[i], 256));
+    L->o_dst = o;
+    L->dtotal = o;
+    for (size_t i = 0; i < k; i++)
+        o_out[i] = take(&o, POM_ALIGN_UP(room[i], 256));
+    L->htotal = o;
 }
 
 void pom_layout_walk(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,

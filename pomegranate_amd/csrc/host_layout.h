@@ -147,6 +147,28 @@ void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nl
 void pom_layout_kvget(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
                       const size_t *cap, size_t nreq, size_t keys_bytes, int records, size_t scratch);
 
+/* The staging of a group of k single calls (host_single.c).  The header
+ * arrays, then the inputs, lie alike on both sides and go up in one H2D copy
+ * of [0, o_dst); the outputs lie behind, in the pinned host staging only: the
+ * kernels write them, out_len and status there directly, so nothing but the
+ * rare pre-scan's words is ever copied back. */
+struct single_layout {
+    size_t o_srcoff, o_dstoff;  /* u64 per call */
+    size_t o_srclen, o_dstcap;  /* u32 per call */
+    size_t o_outlen, o_status;  /* u32, i32 per call: read on the host side */
+    size_t o_plen, o_pstatus;   /* u32, i32 per call: the pre-scan's decoded length and status */
+    size_t pre_off, pre_bytes;  /* their span: the D2H behind the pre-scan */
+    size_t o_fb;                /* u32, 1 + k: the decoders' fallback list, count then ids */
+    size_t o_src;               /* the header's end: the first input */
+    size_t o_dst;               /* end of the H2D; host only: the first output */
+    size_t htotal, dtotal;
+};
+
+/* Call i has src_len[i] bytes of input at o_src[i] and room[i] bytes of output
+ * at o_out[i], each 256-byte aligned. */
+void pom_layout_single(struct single_layout *L, size_t k, const size_t *src_len, const size_t *room,
+                       size_t *o_src, size_t *o_out);
+
 /* The ITEs a payload of n bytes can hold: what a walk can emit at the most. */
 size_t pom_walk_max_ites(size_t n);
 

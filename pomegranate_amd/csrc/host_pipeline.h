@@ -1,8 +1,12 @@
 /* host_pipeline.h -- the chunk pipeline of the host batches (lzo_host.c) as
  * the operations that run through it see it (the codec's in lzo_host.c, the
- * record operations' in host_records.c).  Internal to liblzo_mi355x.so. */
+ * record operations' in host_records.c), and the per-thread, per-device
+ * contexts (host_ctx.c) that it and the single calls (host_single.c) run on.
+ * Internal to liblzo_mi355x.so. */
 #ifndef POM_HOST_PIPELINE_H
 #define POM_HOST_PIPELINE_H 1
+
+#include <time.h>
 
 #include <hip/hip_runtime_api.h>
 
@@ -20,8 +24,48 @@ struct slot {
     size_t hcap;
 };
 
+/* A host thread's resources on one device (host_ctx.c): kSlots slots, so that
+ * several chunks are in flight (copies and kernels of some while others are
+ * packed or unpacked on the host). */
+enum { kSlots = 4, kMaxDev = 16 };
+
+struct dctx {
+    int ready;
+    struct slot s[kSlots];
+};
+
 struct tctx;
 struct hbatch;
+
+/* The calling thread's contexts (freed at its exit); NULL without a usable GPU. */
+struct tctx *pom_tctx_get(void);
+/* Its context on `device`, which must be its current device. */
+struct dctx *pom_dctx_get(struct tctx *t, int device);
+/* At least dbytes of device and hbytes of pinned host staging in the slot. */
+int pom_slot_reserve(struct slot *t, size_t dbytes, size_t hbytes);
+/* The slot lone single calls use: slot 0 on the calling thread's current device. */
+struct slot *pom_single_slot(void);
+
+/* The latency decoder (lzo1x_decode_lat.hip: the whole GPU on a few blocks)
+ * over nb blocks, when there are at most kLatGroup of them, each of at least
+ * sc_lat_min (debug key, default 2048) compressed bytes, and their scratch
+ * fits: one pipeline, the blocks side by side in every kernel, on the
+ * device's shared scratch.  src_off, z, dst_off and cap are host arrays; the
+ * fallback list (count at fb, ids) must be zero on the stream before it.
+ * Blocks it hands over get status LZO_MI355X_DEC_PENDING: the caller runs the
+ * exact decoder behind it.  1 launched, 0 not eligible (nothing launched: the
+ * caller's other decoders), -1 on a launch error. */
+enum { kLatGroup = 8 };
+int pom_lat_decode(const uint8_t *src, const uint64_t *src_off, const uint32_t *z, uint8_t *dst,
+                   const uint64_t *dst_off, const uint32_t *cap, uint32_t nb, uint32_t *out_len,
+                   int32_t *status, uint32_t *fb, uint32_t *ids, hipStream_t s);
+
+static inline double pom_now_ms(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
 
 /* One operation of the host batches.  The pipeline (dev_run) cuts a device's
  * blocks into chunks and, per chunk, on the chunk's slot:

@@ -1,18 +1,10 @@
 /*
- * lzo_host.c -- host side of liblzo_mi355x.so, in C like the reference.
- *
- * Implements the minilzo.h call surface (lzo_init, lzo1x_1_compress,
- * lzo1x_decompress, lzo1x_decompress_safe; reference lib/minilzo.c) and the
- * batch API of lzo_mi355x.h on top of the HIP kernels.  Every codec call runs
- * on the GPU; there is no CPU codec in this library.  A call made without a
- * usable GPU returns LZO_E_ERROR and says why on stderr once.
- *
- * Threading: callers are MDS commit/service threads, the MDSL
- * GC thread and client threads.  Each host thread gets, on each GPU it uses,
- * two HIP streams with their own device/pinned staging (grown on demand up to
- * one chunk, freed at thread exit), so concurrent calls never share device
- * state.  A host batch spreads over the GPUs on one helper thread per GPU
- * (batch_split.c), which use the calling thread's per-GPU resources.
+ * lzo_host.c -- the batch API of lzo_mi355x.h on top of the HIP kernels, in C
+ * like the reference: the device-resident entry points, and the host batches'
+ * chunk pipeline with the codec's three operations.  Every codec call runs on
+ * the GPU; there is no CPU codec in this library.  The threads' contexts are
+ * host_ctx.c's, the minilzo.h single calls host_single.c's, the record
+ * operations host_records.c's, the debug keys host_debug.c's.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -26,228 +18,11 @@
 #include "lzo_mi355x.h"
 #include "minilzo.h"
 
-/* Debug and experiment switches: ONE environment variable, POM_LZO_DEBUG,
- * a comma-separated list of key=value.  No product path
- * needs it; an unset key takes its default.  Keys: decoder=fast|win
- * (device batches), sc_copy=1, sc_combine=0, sc_lat=0, sc_lat_min=BYTES,
- * sc_trace=1, host_timing=1, slots=N, chunk_mb=N, dec_small_first=0, ooo=0, enc_lds_max=N, enc_waves=1|2,
- * enc_grid=N, fail_chunk=K (tests: a device's K-th chunk delivery fails).  The variable is read once, at the first use, into a private
- * copy; lzo_mi355x_debug_reload() reads it again (tests change it between
- * calls).  So the hot paths never call getenv.  Each (re)load publishes a new,
- * immutable copy through one atomic pointer, so a lookup on any thread reads
- * either the old or the new string whole, never one being rewritten (ADVICE
- * r5); the replaced copies are not freed (a reload is a test-time event and a
- * lookup may still be reading one). */
-static pthread_mutex_t dbg_mu = PTHREAD_MUTEX_INITIALIZER;
-static const char *dbg_cur;
-
-static void dbg_load(int always)
-{
-    pthread_mutex_lock(&dbg_mu);
-    if (always || !dbg_cur) {
-        const char *e = getenv("POM_LZO_DEBUG");
-        char *copy = strdup(e ? e : "");
-        if (copy)
-            __atomic_store_n(&dbg_cur, copy, __ATOMIC_RELEASE);
-    }
-    pthread_mutex_unlock(&dbg_mu);
-}
-
-void lzo_mi355x_debug_reload(void)
-{
-    dbg_load(1);
-}
-
-const char *pom_dbg_str(const char *key, char *buf, size_t n)
-{
-    const char *e = __atomic_load_n(&dbg_cur, __ATOMIC_ACQUIRE);
-    if (!e) {
-        dbg_load(0);                              /* first use */
-        e = __atomic_load_n(&dbg_cur, __ATOMIC_ACQUIRE);
-    }
-    if (!e || !*e || !n)
-        return NULL;
-    const size_t kl = strlen(key);
-    for (const char *p = e; *p;) {
-        const char *end = strchr(p, ',');
-        const size_t len = end ? (size_t)(end - p) : strlen(p);
-        if (len > kl && strncmp(p, key, kl) == 0 && p[kl] == '=') {
-            size_t vl = len - kl - 1;
-            if (vl >= n)
-                vl = n - 1;
-            memcpy(buf, p + kl + 1, vl);
-            buf[vl] = 0;
-            return buf;
-        }
-        if (!end)
-            break;
-        p = end + 1;
-    }
-    return NULL;
-}
-
-long pom_dbg_int(const char *key, long dflt)
-{
-    char buf[32];
-    const char *v = pom_dbg_str(key, buf, sizeof buf);
-    return v && *v ? atol(v) : dflt;
-}
-
 #define ALIGN_UP(x, a) POM_ALIGN_UP(x, a)
-
-/* ------------------------------------------------------------------------ */
-/* GPU availability (checked once per process)                              */
-/* ------------------------------------------------------------------------ */
-static pthread_once_t gpu_once = PTHREAD_ONCE_INIT;
-static int gpu_count;
-
-static void gpu_probe(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        fprintf(stderr, "liblzo_mi355x: no usable GPU (hipGetDeviceCount=%d); "
-                        "the MI355X LZO1X codec has no CPU fallback\n", n);
-        n = 0;
-    }
-    gpu_count = n;
-}
-
-int lzo_mi355x_device_count(void)
-{
-    pthread_once(&gpu_once, gpu_probe);
-    return gpu_count;
-}
 
 size_t lzo_mi355x_worst_compress(size_t n)
 {
     return n + n / 16 + 64 + 3;
-}
-
-/* ------------------------------------------------------------------------ */
-/* Per-thread, per-device streams and staging                               */
-/* ------------------------------------------------------------------------ */
-
-/* A host thread's resources on one device: kSlots slots, so that several
- * chunks are in flight (copies and kernels of some while others are packed
- * or unpacked on the host). */
-enum { kSlots = 4 };
-
-struct dctx {
-    int ready;
-    struct slot s[kSlots];
-};
-
-enum { kMaxDev = 16 };
-
-struct tctx {
-    struct dctx dev[kMaxDev];
-};
-
-static pthread_key_t tkey;
-static pthread_once_t tkey_once = PTHREAD_ONCE_INIT;
-
-static void tctx_free(void *p)
-{
-    struct tctx *t = p;
-    if (!t)
-        return;
-    for (int d = 0; d < kMaxDev; d++) {
-        struct dctx *c = &t->dev[d];
-        if (!c->ready)
-            continue;
-        hipSetDevice(d);
-        for (int k = 0; k < kSlots; k++) {
-            if (c->s[k].dmem)
-                hipFree(c->s[k].dmem);
-            if (c->s[k].hmem)
-                hipHostFree(c->s[k].hmem);
-            hipStreamDestroy(c->s[k].stream);
-        }
-    }
-    free(t);
-}
-
-static void tkey_make(void)
-{
-    pthread_key_create(&tkey, tctx_free);
-}
-
-static struct tctx *tctx_get(void)
-{
-    if (lzo_mi355x_device_count() <= 0)
-        return NULL;
-    pthread_once(&tkey_once, tkey_make);
-    struct tctx *t = pthread_getspecific(tkey);
-    if (!t) {
-        t = calloc(1, sizeof(*t));
-        if (!t)
-            return NULL;
-        pthread_setspecific(tkey, t);
-    }
-    return t;
-}
-
-/* The calling thread's context on `device`, which must be its current device. */
-static struct dctx *dctx_get(struct tctx *t, int device)
-{
-    if (device < 0 || device >= kMaxDev)
-        return NULL;
-    struct dctx *c = &t->dev[device];
-    if (!c->ready) {
-        for (int k = 0; k < kSlots; k++)
-            if (hipStreamCreateWithFlags(&c->s[k].stream, hipStreamNonBlocking) != hipSuccess) {
-                while (k-- > 0)
-                    hipStreamDestroy(c->s[k].stream);
-                return NULL;
-            }
-        c->ready = 1;
-    }
-    return c;
-}
-
-static int slot_reserve(struct slot *t, size_t dbytes, size_t hbytes)
-{
-    /* growth: +25%, or doubling up to 64 MiB (combined single calls grow
-     * their groups step by step; each regrowth is a hipMalloc/hipHostMalloc) */
-    const size_t kDoubleMax = (size_t)64 << 20;
-    if (dbytes > t->dcap) {
-        const size_t old = t->dcap;
-        if (t->dmem)
-            hipFree(t->dmem);
-        t->dmem = NULL;
-        t->dcap = 0;
-        size_t want = ALIGN_UP(dbytes + dbytes / 4, 1 << 20);
-        if (want < 2 * old && 2 * old <= kDoubleMax)
-            want = 2 * old;
-        if (hipMalloc((void **)&t->dmem, want) != hipSuccess)
-            return -1;
-        t->dcap = want;
-    }
-    if (hbytes > t->hcap) {
-        const size_t old = t->hcap;
-        if (t->hmem)
-            hipHostFree(t->hmem);
-        t->hmem = NULL;
-        t->hcap = 0;
-        size_t want = ALIGN_UP(hbytes + hbytes / 4, 1 << 20);
-        if (want < 2 * old && 2 * old <= kDoubleMax)
-            want = 2 * old;
-        if (hipHostMalloc((void **)&t->hmem, want, hipHostMallocDefault) != hipSuccess)
-            return -1;
-        t->hcap = want;
-    }
-    return 0;
-}
-
-/* The slot single calls use: slot 0 on the calling thread's current device. */
-static struct slot *single_slot(void)
-{
-    struct tctx *t = tctx_get();
-    int dev = 0;
-    if (!t || hipGetDevice(&dev) != hipSuccess)
-        return NULL;
-    struct dctx *c = dctx_get(t, dev);
-    return c ? &c->s[0] : NULL;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -318,7 +93,7 @@ size_t lzo_mi355x_decompress_scratch(uint32_t nblocks)
  * (lzo1x_decode_fast.hip: 16 blocks per CU) or the windowed one
  * (lzo1x_decode_win.hip: 2 blocks per CU, a 64 KiB LDS output ring, never
  * reads its own output back).  Debug key decoder=fast|win forces one;
- * single calls always use the windowed one (see single_call). */
+ * single calls always use the windowed one (host_single.c). */
 enum { DEC_FAST = 0, DEC_WIN = 1 };
 static int use_win_decoder(uint32_t nblocks)
 {
@@ -333,40 +108,15 @@ static int use_win_decoder(uint32_t nblocks)
     return nblocks <= 2u * (cus ? cus : 256u);
 }
 
-/* Single calls: the kernels write the output and its length/status straight
- * into the pinned host staging (hipHostMalloc, mapped into the device's
- * address space), so nothing is copied back but what was produced; the
- * caller reads it only after the stream synchronisation, which is what makes
- * the kernels' writes visible to the host.  debug key sc_copy=1: the round-2
- * path (device staging, one D2H copy of the whole room). */
-static int sc_zero_copy(void)
-{
-    return pom_dbg_int("sc_copy", 0) != 1;
-}
-
 /* Throughput decoder over the whole batch, then the exact decoder over the blocks
  * it refused (malformed input, capacity/lookbehind errors, pathological
  * streams).  Without scratch every block takes the exact decoder.
  * unchecked: the exact decoder follows the unchecked lzo1x_decompress (the
  * fast decoder only ever finishes streams on which both agree). */
-static int decompress_dev_with(const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
-                               uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap,
-                               uint32_t *out_len, int32_t *status, uint32_t nblocks, void *scratch,
-                               int unchecked, int win, hipStream_t s);
-
 static int decompress_dev(const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
                           uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap,
                           uint32_t *out_len, int32_t *status, uint32_t nblocks, void *scratch,
                           int unchecked, hipStream_t s)
-{
-    return decompress_dev_with(src, src_off, src_len, dst, dst_off, dst_cap, out_len, status,
-                               nblocks, scratch, unchecked, use_win_decoder(nblocks), s);
-}
-
-static int decompress_dev_with(const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
-                               uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap,
-                               uint32_t *out_len, int32_t *status, uint32_t nblocks, void *scratch,
-                               int unchecked, int win, hipStream_t s)
 {
     if (nblocks == 0)
         return 0;
@@ -377,7 +127,7 @@ static int decompress_dev_with(const uint8_t *src, const uint64_t *src_off, cons
     uint8_t *scr = scratch;
     const uint32_t nsets = (uint32_t)scr_sets(nblocks);
     uint32_t *fb = (uint32_t *)scr, *ids = (uint32_t *)(scr + scr_head(nblocks));
-    if (win) {
+    if (use_win_decoder(nblocks)) {
         /* the windowed decoder: no op sets,
          * only the fallback list */
         if (hipMemsetAsync(scr, 0, 256, s) != hipSuccess)
@@ -552,122 +302,6 @@ int pom_stage_inputs(const struct layout *L, uint8_t *h, const struct hbatch *B)
 /* debug key host_timing=1: per-batch and per-chunk wall times on stderr (diagnostic) */
 #define g_timing (pom_dbg_int("host_timing", 0) == 1)
 
-static double now_ms(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-
-/* The latency decoder's scratch: ONE buffer per device, shared by every
- * thread's host-batch chunks and combined single-call groups (ADVICE round
- * 3: per-thread, per-slot buffers of up to 1 GiB each pinned GBs of HBM).
- * A user holds the mutex while it launches, waits (on the GPU, through the
- * event) for the previous use's kernels, and records its own.  Groups needing
- * more than kLatMaxScratch (from ~1 MB of compressed input) take the windowed
- * decoder. */
-static const size_t kLatMaxScratch = (size_t)256 << 20;
-struct lat_scratch {
-    pthread_mutex_t mu;
-    void *buf;
-    size_t cap;
-    hipEvent_t done;            /* the last use's kernels (created with the buffer) */
-};
-static struct lat_scratch lat_s[kMaxDev];
-static pthread_once_t lat_once = PTHREAD_ONCE_INIT;
-
-static void lat_init(void)
-{
-    for (int d = 0; d < kMaxDev; d++)
-        pthread_mutex_init(&lat_s[d].mu, NULL);
-}
-
-/* The device's scratch, at least `bytes`, locked, with stream s ordered
- * after its last use; NULL (unlocked) if the device or memory is missing. */
-static struct lat_scratch *lat_acquire(size_t bytes, hipStream_t s)
-{
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev || bytes > kLatMaxScratch)
-        return NULL;
-    pthread_once(&lat_once, lat_init);
-    struct lat_scratch *L = &lat_s[dev];
-    pthread_mutex_lock(&L->mu);
-    if (!L->done && hipEventCreateWithFlags(&L->done, hipEventDisableTiming) != hipSuccess) {
-        L->done = NULL;
-        pthread_mutex_unlock(&L->mu);
-        return NULL;
-    }
-    if (L->cap < bytes) {
-        hipEventSynchronize(L->done);           /* (a never-recorded event is complete) */
-        if (L->buf)
-            hipFree(L->buf);
-        L->buf = NULL;
-        L->cap = 0;
-        size_t want = ALIGN_UP(bytes + bytes / 4, (size_t)1 << 20);
-        want = want < kLatMaxScratch ? want : kLatMaxScratch;
-        if (hipMalloc(&L->buf, want) != hipSuccess) {
-            L->buf = NULL;
-            pthread_mutex_unlock(&L->mu);
-            return NULL;
-        }
-        L->cap = want;
-    }
-    if (hipStreamWaitEvent(s, L->done, 0) != hipSuccess) {
-        pthread_mutex_unlock(&L->mu);
-        return NULL;
-    }
-    return L;
-}
-
-static void lat_release(struct lat_scratch *L, hipStream_t s)
-{
-    hipEventRecord(L->done, s);
-    pthread_mutex_unlock(&L->mu);
-}
-
-static int use_lat_decoder(size_t z);
-
-/* A decompress chunk of at most 8 blocks, each of at least sc_lat_min (debug key, default 2048)
- * compressed bytes, decodes on one latency-decoder pipeline (the whole GPU on
- * these few blocks; lzo1x_decode_lat.hip) with the exact decoder behind it for
- * the blocks it hands over.  1 launched, 0 not eligible (nothing launched),
- * -1 on an error. */
-static int lat_chunk(const struct layout *L, const uint8_t *h, uint8_t *d, hipStream_t s)
-{
-    const uint32_t nb = (uint32_t)L->nb;
-    if (nb == 0 || nb > 8)
-        return 0;
-    const uint64_t *so = (const uint64_t *)(h + L->o_srcoff);
-    const uint64_t *dof = (const uint64_t *)(h + L->o_dstoff);
-    const uint32_t *sl = (const uint32_t *)(h + L->o_srclen);
-    const uint32_t *dc = (const uint32_t *)(h + L->o_dstcap);
-    for (uint32_t i = 0; i < nb; i++)
-        if (!use_lat_decoder(sl[i]))
-            return 0;
-    const size_t need = lzo_mi355x_decompress_lat_scratch_n(so, sl, dc, nb);
-    if (need == 0 || need > kLatMaxScratch)
-        return 0;
-    uint8_t *scr = d + L->o_scr;
-    uint32_t *fb = (uint32_t *)scr, *ids = (uint32_t *)(scr + scr_head(nb));
-    uint32_t *ol = (uint32_t *)(d + L->o_outlen);
-    int32_t *st = (int32_t *)(d + L->o_status);
-    if (hipMemsetAsync(scr, 0, 256, s) != hipSuccess)
-        return -1;
-    struct lat_scratch *LS = lat_acquire(need, s);
-    if (!LS)
-        return 0;                               /* (the chunk's usual decoders) */
-    const int lrc = lzo_mi355x_launch_decompress_lat_n(d + L->o_src, so, sl, d + L->o_dst, dof, dc, nb, ol, st,
-                                                       fb, ids, 0, LS->buf, LS->cap, s);
-    lat_release(LS, s);
-    if (lrc != 0 ||
-        lzo_mi355x_launch_decompress_exact(d + L->o_src, (const uint64_t *)(d + L->o_srcoff),
-                                           (const uint32_t *)(d + L->o_srclen), d + L->o_dst,
-                                           (const uint64_t *)(d + L->o_dstoff), (const uint32_t *)(d + L->o_dstcap),
-                                           ol, st, fb, ids, nb, nb, 0, s) != 0)
-        return -1;
-    return 1;
-}
-
 /* The chunk's blocks as the kernels take them: pointers into the device staging. */
 struct dev_blocks {
     const uint8_t *src;
@@ -758,8 +392,26 @@ static int compress_kernels(struct slot *S, const struct layout *L, const struct
 static int decompress_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
 {
     (void)B;
-    const int lat = lat_chunk(L, S->hmem, S->dmem, S->stream);
-    return codec_lengths_back(S, L, lat < 0 ? -1 : lat > 0 ? 0 : pom_decode_lzo_blocks(S, L, 0));
+    /* a chunk of a few large blocks: the latency decoder (pom_lat_decode takes
+     * the host side's arrays), its fallback list at the scratch's head zeroed
+     * first, with the exact decoder behind it for the blocks it hands over;
+     * every other chunk: the throughput decoders */
+    const struct dev_blocks D = dev_blocks(S, L);
+    const uint8_t *h = S->hmem;
+    const uint32_t nb = (uint32_t)L->nb;
+    uint8_t *scr = S->dmem + L->o_scr;
+    uint32_t *fb = (uint32_t *)scr, *ids = (uint32_t *)(scr + scr_head(nb));
+    int rc = hipMemsetAsync(scr, 0, 256, S->stream) == hipSuccess ? 0 : -1;
+    if (rc == 0)
+        rc = pom_lat_decode(D.src, (const uint64_t *)(h + L->o_srcoff), (const uint32_t *)(h + L->o_srclen), D.dst,
+                            (const uint64_t *)(h + L->o_dstoff), (const uint32_t *)(h + L->o_dstcap), nb, D.ol,
+                            D.st, fb, ids, S->stream);
+    if (rc > 0)
+        rc = lzo_mi355x_launch_decompress_exact(D.src, D.so, D.sl, D.dst, D.dof, D.dc, D.ol, D.st, fb, ids, nb, nb,
+                                                0, S->stream);
+    else if (rc == 0)
+        rc = pom_decode_lzo_blocks(S, L, 0);
+    return codec_lengths_back(S, L, rc);
 }
 
 static int concat_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
@@ -860,13 +512,13 @@ static const struct chunk_ops concat_ops = {
  * no sizing -- all queued on the slot's stream, nothing waited for. */
 static int chunk_launch(struct slot *S, struct layout *L, const struct hbatch *B)
 {
-    if (slot_reserve(S, L->dtotal, L->htotal) != 0)
+    if (pom_slot_reserve(S, L->dtotal, L->htotal) != 0)
         return -1;
-    const double t0 = g_timing ? now_ms() : 0;
+    const double t0 = g_timing ? pom_now_ms() : 0;
     if (B->ops->stage(L, S->hmem, B) != 0)
         return -1;
     if (g_timing)
-        fprintf(stderr, "  chunk n=%zu: fill %.2f ms (%zu B)\n", L->nb, now_ms() - t0, L->htotal);
+        fprintf(stderr, "  chunk n=%zu: fill %.2f ms (%zu B)\n", L->nb, pom_now_ms() - t0, L->htotal);
     if (hipMemcpyAsync(S->dmem, S->hmem, L->o_dst, hipMemcpyHostToDevice, S->stream) != hipSuccess)
         return -1;
     return B->ops->kernels(S, L, B);
@@ -893,16 +545,16 @@ static int chunk_collect(struct slot *S, struct layout *L, const struct hbatch *
 static int chunk_deliver(struct slot *S, struct layout *L, const struct hbatch *B,
                          struct slot *nS, struct layout *nL)
 {
-    const double t0 = g_timing ? now_ms() : 0;
+    const double t0 = g_timing ? pom_now_ms() : 0;
     if (chunk_collect(S, L, B) != 0 || hipStreamSynchronize(S->stream) != hipSuccess)
         return -1;
     if (nS && chunk_collect(nS, nL, B) != 0)
         return -1;
-    const double t1 = g_timing ? now_ms() : 0;
+    const double t1 = g_timing ? pom_now_ms() : 0;
     const int rc = B->ops->unpack(S, L, B);
     if (g_timing)
         fprintf(stderr, "  deliver n=%zu: wait %.2f (%zu B) unpack %.2f ms\n", L->nb, t1 - t0,
-                L->packed, now_ms() - t1);
+                L->packed, pom_now_ms() - t1);
     return rc;
 }
 
@@ -947,7 +599,7 @@ static int dev_run(void *arg, int d)
     if (prev_dev != device && hipSetDevice(device) != hipSuccess)
         return -1;
     int rc = 0;
-    struct dctx *c = dctx_get(B->t, device);
+    struct dctx *c = pom_dctx_get(B->t, device);
     if (!c) {
         rc = -1;
     } else {
@@ -1040,10 +692,10 @@ static int dev_run(void *arg, int d)
             /* the caller's per-chunk work runs while the launched chunks' copies
              * and kernels are in flight */
             if (done_ids && B->on_chunk) {
-                const double tc = g_timing ? now_ms() : 0;
+                const double tc = g_timing ? pom_now_ms() : 0;
                 B->on_chunk(B->cb_ctx, done_ids, done_nb);
                 if (g_timing)
-                    fprintf(stderr, "  on_chunk n=%zu: %.2f ms\n", done_nb, now_ms() - tc);
+                    fprintf(stderr, "  on_chunk n=%zu: %.2f ms\n", done_nb, pom_now_ms() - tc);
             }
             if (!(from < nids && rc == 0)) {
                 int any = 0;
@@ -1089,8 +741,8 @@ static int batch_devices(int *devs)
 int pom_host_batch(struct hbatch *B, size_t nblocks)
 {
     const struct chunk_ops *ops = B->ops;
-    const double t0 = g_timing ? now_ms() : 0;
-    B->t = tctx_get();
+    const double t0 = g_timing ? pom_now_ms() : 0;
+    B->t = pom_tctx_get();
     if (!B->t)
         return LZO_E_ERROR;
     if (nblocks == 0)
@@ -1148,7 +800,7 @@ int pom_host_batch(struct hbatch *B, size_t nblocks)
         rc = pom_run_devices(B->plan.ndev, dev_run, B) == 0 ? LZO_E_OK : LZO_E_ERROR;
         if (g_timing)
             fprintf(stderr, "pom host %s n=%zu devices=%d: %.2f ms\n", ops->label, nblocks, B->plan.ndev,
-                    now_ms() - t0);
+                    pom_now_ms() - t0);
         pom_plan_free(&B->plan);
     }
     free(cap);
@@ -1206,534 +858,4 @@ int lzo_mi355x_decompress_concat_batch(const uint8_t *const *src, const size_t *
                                        size_t nblocks)
 {
     return codec_batch(&concat_ops, src, src_len, dst, dst_len, status, nblocks, NULL, NULL, NULL);
-}
-
-/* ------------------------------------------------------------------------ */
-/* minilzo.h call surface                                                   */
-/* ------------------------------------------------------------------------ */
-
-/* lib/minilzo.c:2567-2598: a zero version or a type-size mismatch is
- * LZO_E_ERROR; additionally the GPU must be usable. */
-int __lzo_init_v2(unsigned v, int s1, int s2, int s3, int s4, int s5, int s6, int s7, int s8,
-                  int s9)
-{
-    if (v == 0)
-        return LZO_E_ERROR;
-    int ok = (s1 == -1 || s1 == (int)sizeof(short)) && (s2 == -1 || s2 == (int)sizeof(int)) &&
-             (s3 == -1 || s3 == (int)sizeof(long)) &&
-             (s4 == -1 || s4 == (int)sizeof(lzo_uint32)) &&
-             (s5 == -1 || s5 == (int)sizeof(lzo_uint)) &&
-             (s6 == -1 || s6 == (int)lzo_sizeof_dict_t) &&
-             (s7 == -1 || s7 == (int)sizeof(char *)) &&
-             (s8 == -1 || s8 == (int)sizeof(lzo_voidp)) &&
-             (s9 == -1 || s9 == (int)sizeof(lzo_callback_t));
-    if (!ok)
-        return LZO_E_ERROR;
-    return lzo_mi355x_device_count() > 0 ? LZO_E_OK : LZO_E_ERROR;
-}
-
-unsigned lzo_version(void) { return LZO_VERSION; }
-const char *lzo_version_string(void) { return LZO_VERSION_STRING; }
-const char *lzo_version_date(void) { return LZO_VERSION_DATE; }
-lzo_charp _lzo_version_string(void) { return (lzo_charp)LZO_VERSION_STRING; }
-lzo_charp _lzo_version_date(void) { return (lzo_charp)LZO_VERSION_DATE; }
-/* lib/minilzo.c:2306-2314 (minilzo builds return LZO_VERSION_STRING) */
-lzo_bytep lzo_copyright(void) { return (lzo_bytep)LZO_VERSION_STRING; }
-
-/* Host utilities of the reference's minilzo.c (lib/minilzo.c:2355-2500). */
-int lzo_memcmp(const lzo_voidp a, const lzo_voidp b, lzo_uint len) { return memcmp(a, b, len); }
-lzo_voidp lzo_memcpy(lzo_voidp dst, const lzo_voidp src, lzo_uint len) { return memcpy(dst, src, len); }
-lzo_voidp lzo_memmove(lzo_voidp dst, const lzo_voidp src, lzo_uint len) { return memmove(dst, src, len); }
-lzo_voidp lzo_memset(lzo_voidp buf, int c, lzo_uint len) { return memset(buf, c, len); }
-
-lzo_uint32 lzo_adler32(lzo_uint32 c, const lzo_bytep buf, lzo_uint len)
-{
-    if (buf == NULL)
-        return 1;
-    uint32_t lo = c & 0xffffu, hi = (c >> 16) & 0xffffu;
-    const unsigned char *p = buf;
-    while (len > 0) {
-        /* 5552 bytes keep both sums below 2^32 before the reduction */
-        lzo_uint k = len < 5552 ? len : 5552;
-        len -= k;
-        for (lzo_uint i = 0; i < k; i++) {
-            lo += p[i];
-            hi += lo;
-        }
-        p += k;
-        lo %= 65521u;
-        hi %= 65521u;
-    }
-    return (hi << 16) | lo;
-}
-
-int _lzo_config_check(void)
-{
-    union {
-        unsigned long a[2];
-        unsigned char b[2 * sizeof(unsigned long)];
-    } u;
-    u.a[0] = u.a[1] = 0;
-    u.b[0] = 128;
-    lzo_uint v;
-    memcpy(&v, u.b, sizeof v);
-    return v == 128 ? LZO_E_OK : LZO_E_ERROR;       /* little-endian, as the codec assumes */
-}
-
-lzo_uintptr_t __lzo_ptr_linear(const lzo_voidp ptr) { return (lzo_uintptr_t)ptr; }
-
-unsigned __lzo_align_gap(const lzo_voidp p, lzo_uint size)
-{
-    const lzo_uintptr_t a = (lzo_uintptr_t)p;
-    return size ? (unsigned)(((a + size - 1) / size) * size - a) : 0u;
-}
-
-/* ---- single calls ------------------------------------------------------------
- * The minilzo.h entry points code one block per call, synchronously.  Calls
- * that arrive together from several threads on the same GPU (the MDS commit
- * threads, mds/txg.c:1010-1011, and the service threads that load ITBs,
- * mds/itb.c:2964) are COMBINED: the first caller becomes the leader and runs
- * every call queued behind it (of the same kind, up to kScGroup) as one
- * launch on its own stream; the others sleep until their result is in their
- * buffer.  A lone call is a group of one.  Debug key sc_combine=0 turns combining
- * off (every call its own launch, as in round 2).
- * Staging of a group of k calls (device and pinned host alike):
- *   [0, H)          header arrays: src_off u64[k], dst_off u64[k], src_len[k],
- *                   dst_cap[k], out_len[k], status[k], pre-scan length[k] and
- *                   status[k], the decoder's fallback list (count + k ids)
- *   [H, I)          the inputs, 256-byte aligned
- *   [I, J)          the outputs (each: worst case, the caller's capacity or a
- *                   guess); with zero copy they are written to the host side only
- * One H2D copy ([0, I)), one kernel, one synchronisation: the windowed decoder
- * refuses few valid streams, so the exact decoder runs only when a status says
- * a block was handed over.
- */
-enum { kScGroup = 64 };
-static const size_t kScGroupBytes = (size_t)256 << 20;
-
-enum sc_kind { SC_COMPRESS, SC_SAFE, SC_UNCHECKED };
-
-struct sc_req {
-    enum sc_kind kind;
-    const uint8_t *src;
-    size_t src_len;
-    uint8_t *dst;
-    size_t room;
-    size_t produced;
-    int rc;
-    int done;
-    uint64_t group;             /* sequence number of the group that ran it */
-    struct sc_req *next;
-};
-
-struct sc_queue {
-    pthread_mutex_t mu;
-    pthread_cond_t cv;
-    struct sc_req *head, *tail;
-    int leader;
-    int last_k;                 /* size of the last group (a hint that callers come together) */
-    uint64_t seq;               /* groups run so far */
-    int ready;                  /* slot and stream below created */
-    struct slot slot;           /* the groups' staging: one leader at a time per device */
-};
-
-static struct sc_queue sc_q[kMaxDev];
-static __thread uint64_t sc_last_group[kMaxDev];   /* per device: group of this thread's last single call */
-static pthread_once_t sc_once = PTHREAD_ONCE_INIT;
-
-static void sc_init(void)
-{
-    for (int d = 0; d < kMaxDev; d++) {
-        pthread_mutex_init(&sc_q[d].mu, NULL);
-        /* the leader's ~50 us wait for company is a relative time: measure
-         * it on CLOCK_MONOTONIC, which wall-clock adjustments do not move */
-        pthread_condattr_t ca;
-        pthread_condattr_init(&ca);
-        pthread_condattr_setclock(&ca, CLOCK_MONOTONIC);
-        pthread_cond_init(&sc_q[d].cv, &ca);
-        pthread_condattr_destroy(&ca);
-    }
-}
-
-static int sc_combine(void)
-{
-    return pom_dbg_int("sc_combine", 1) != 0;
-}
-
-/* header arrays of a group of k */
-struct sc_hdr {
-    uint64_t *src_off, *dst_off;
-    uint32_t *src_len, *dst_cap, *out_len;
-    int32_t *status;
-    uint32_t *plen;
-    int32_t *pstatus;
-    uint32_t *fb;               /* the decoder's fallback list: count, then k ids */
-};
-
-static size_t sc_hdr_bytes(int k)
-{
-    return ALIGN_UP((size_t)k * 44 + 4, 256);
-}
-
-static struct sc_hdr sc_hdr_at(uint8_t *base, int k)
-{
-    struct sc_hdr x;
-    x.src_off = (uint64_t *)base;
-    x.dst_off = x.src_off + k;
-    x.src_len = (uint32_t *)(x.dst_off + k);
-    x.dst_cap = x.src_len + k;
-    x.out_len = x.dst_cap + k;
-    x.status = (int32_t *)(x.out_len + k);
-    x.plen = (uint32_t *)(x.status + k);
-    x.pstatus = (int32_t *)(x.plen + k);
-    x.fb = (uint32_t *)(x.pstatus + k);
-    return x;
-}
-
-/* One launch for the k calls g[0..k) (all of one kind) on the calling thread's
- * slot: fills each call's rc and produced length and copies its output. */
-/* The staging of combined groups on the calling thread's device: the leader
- * flag gives one group at a time per device, so one slot serves every thread
- * (per-thread slots each grew to the groups their thread happened to lead,
- * and every regrowth is a hipMalloc / hipHostMalloc). */
-static struct slot *sc_slot(struct sc_queue *q)
-{
-    if (!q)
-        return single_slot();
-    if (!q->ready) {
-        if (hipStreamCreateWithFlags(&q->slot.stream, hipStreamNonBlocking) != hipSuccess)
-            return NULL;
-        q->ready = 1;
-    }
-    return &q->slot;
-}
-
-/* A decode whose compressed block is at least this long takes the latency
- * decoder (lzo1x_decode_lat.hip: the whole GPU on one block, 0.11-0.14 ms from
- * 32 KiB up to 536 KB, where the windowed decoder's one workgroup takes
- * 0.14-2.2 ms); shorter ones (equal at 12 KB) the windowed decoder, and so
- * does a combined group with any such call or more than 8 calls (see
- * lat_group).  Debug keys: sc_lat_min sets the threshold (bytes of compressed
- * input), sc_lat=0 turns it off. */
-static int use_lat_decoder(size_t z)
-{
-    const long min_z = pom_dbg_int("sc_lat", 1) == 0 ? 0x7FFFFFFFL : pom_dbg_int("sc_lat_min", 2048L);
-    return z >= (size_t)(min_z > 0 ? min_z : 2048L);
-}
-
-
-/* A group of k <= 8 decodes of at least sc_lat_min compressed bytes each
- * runs as ONE latency-decoder pipeline (lzo1x_decode_lat.hip: the blocks side
- * by side in every kernel).  Returns 1 when launched, 0 when the group does
- * not qualify (nothing launched), -1 on a launch error.  (Separate pipelines
- * on four streams were measured first: they did not overlap -- three 64 KiB
- * blocks 0.38 ms against 0.19 for one.) */
-enum { kLatGroup = 8 };
-
-static int lat_group(struct slot *t, struct sc_req **g, int k, const uint8_t *d, uint8_t *out,
-                     const size_t *o_src, const size_t *o_out, uint32_t *olen, int32_t *ost, uint32_t *fb,
-                     hipStream_t s)
-{
-    if (k > kLatGroup)
-        return 0;
-    uint64_t so[kLatGroup], doff[kLatGroup];
-    uint32_t z[kLatGroup], cap[kLatGroup];
-    for (int i = 0; i < k; i++) {
-        if (!use_lat_decoder(g[i]->src_len) || g[i]->room > 0xFFFFFFFFu)
-            return 0;
-        so[i] = o_src[i];
-        doff[i] = o_out[i];
-        z[i] = (uint32_t)g[i]->src_len;
-        cap[i] = (uint32_t)g[i]->room;
-    }
-    (void)t;
-    const size_t need = lzo_mi355x_decompress_lat_scratch_n(so, z, cap, (uint32_t)k);
-    if (need == 0 || need > kLatMaxScratch)
-        return 0;                               /* out of its range: the windowed decoder */
-    struct lat_scratch *LS = lat_acquire(need, s);
-    if (!LS)
-        return 0;
-    const int rc = lzo_mi355x_launch_decompress_lat_n(d, so, z, out, doff, cap, (uint32_t)k, olen, ost, fb, fb + 1,
-                                                      0, LS->buf, LS->cap, s);
-    lat_release(LS, s);
-    return rc == 0 ? 1 : -1;
-}
-
-static void sc_run_group(struct sc_req **g, int k, struct sc_queue *q)
-{
-    const enum sc_kind kind = g[0]->kind;
-    const int trace = pom_dbg_int("sc_trace", 0) == 1;
-    const double t0 = trace ? now_ms() : 0.0;
-    for (int i = 0; i < k; i++)
-        g[i]->rc = LZO_E_ERROR;
-    struct slot *t = sc_slot(q);
-    if (!t)
-        return;
-    const int zc = sc_zero_copy();
-    const size_t H = sc_hdr_bytes(k);
-    size_t o = H, o_out[kScGroup], o_src[kScGroup];
-    for (int i = 0; i < k; i++) {
-        o_src[i] = o;
-        o += ALIGN_UP(g[i]->src_len, 256);
-    }
-    const size_t I = o;
-    for (int i = 0; i < k; i++) {
-        o_out[i] = o;
-        o += ALIGN_UP(g[i]->room, 256);
-    }
-    const size_t J = o;
-    if (slot_reserve(t, J, J) != 0)
-        return;
-    uint8_t *h = t->hmem, *d = t->dmem;
-    hipStream_t s = t->stream;
-    struct sc_hdr hh = sc_hdr_at(h, k), dh = sc_hdr_at(d, k);
-    memset(h, 0, H);
-    for (int i = 0; i < k; i++) {
-        hh.src_off[i] = o_src[i];
-        hh.dst_off[i] = o_out[i];
-        hh.src_len[i] = (uint32_t)g[i]->src_len;
-        hh.dst_cap[i] = (uint32_t)g[i]->room;
-        hh.status[i] = -1;
-        if (g[i]->src_len)
-            memcpy(h + o_src[i], g[i]->src, g[i]->src_len);
-    }
-    if (hipMemcpyAsync(d, h, I, hipMemcpyHostToDevice, s) != hipSuccess)
-        return;
-    /* zero copy: outputs, out_len and status land in the pinned host staging */
-    uint8_t *out = zc ? h : d;
-    uint32_t *olen = zc ? hh.out_len : dh.out_len;
-    int32_t *ost = zc ? hh.status : dh.status;
-    int rc;
-    if (kind == SC_COMPRESS) {
-        /* no scratch: the LDS-dictionary encoder, faster for a few blocks; the
-         * general encoder's pass only for a block over 16 MiB */
-        int big = 0;
-        for (int i = 0; i < k; i++)
-            big |= g[i]->src_len > LZO_MI355X_FAST_MAX_N;
-        rc = lzo_mi355x_launch_compress_fast(d, dh.src_off, dh.src_len, out, dh.dst_off, dh.dst_cap, olen,
-                                             ost, (uint32_t)k, NULL, 0, s);
-        if (rc == 0 && big)
-            rc = lzo_mi355x_launch_compress(d, dh.src_off, dh.src_len, out, dh.dst_off, dh.dst_cap, olen, ost,
-                                            (uint32_t)k, 1, s);
-    } else {
-        /* SC_UNCHECKED: decoded into the room; the unchecked decoder never
-         * reports an output overrun (lib/minilzo.c:3676-3680), so
-         * OUTPUT_OVERRUN here means the stream is longer than the room.
-         * The windowed decoder never reads its output back (host memory);
-         * its fallback list lives in the header (zeroed by the H2D copy). */
-        const int lat = lat_group(t, g, k, d, out, o_src, o_out, olen, ost, dh.fb, s);
-        rc = lat < 0   ? -1
-             : lat > 0 ? 0
-                       : lzo_mi355x_launch_decompress_win(d, dh.src_off, dh.src_len, out, dh.dst_off,
-                                                          dh.dst_cap, olen, ost, dh.fb, dh.fb + 1,
-                                                          (uint32_t)k, s);
-    }
-    /* (copy mode: lengths and statuses, then the outputs) */
-    if (rc != 0 ||
-        (!zc && (hipMemcpyAsync(h + k * 16, d + k * 16, (size_t)k * 16, hipMemcpyDeviceToHost, s) !=
-                     hipSuccess ||
-                 hipMemcpyAsync(h + I, d + I, J - I, hipMemcpyDeviceToHost, s) != hipSuccess)) ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return;
-    if (kind != SC_COMPRESS) {
-        int handed = 0;
-        for (int i = 0; i < k; i++)
-            handed |= hh.status[i] == LZO_MI355X_DEC_PENDING;
-        if (handed &&
-            (lzo_mi355x_launch_decompress_exact(d, dh.src_off, dh.src_len, out, dh.dst_off, dh.dst_cap,
-                                                olen, ost, dh.fb, dh.fb + 1, (uint32_t)k, (uint32_t)k,
-                                                kind == SC_UNCHECKED, s) != 0 ||
-             (!zc && (hipMemcpyAsync(h + k * 16, d + k * 16, (size_t)k * 16, hipMemcpyDeviceToHost, s) !=
-                          hipSuccess ||
-                      hipMemcpyAsync(h + I, d + I, J - I, hipMemcpyDeviceToHost, s) != hipSuccess)) ||
-             hipStreamSynchronize(s) != hipSuccess))
-            return;
-    }
-    int over = 0;
-    for (int i = 0; i < k; i++)
-        over |= kind == SC_UNCHECKED && hh.status[i] == LZO_E_OUTPUT_OVERRUN;
-    if (over) {
-        /* rare: the decoded lengths (inputs still on the GPU); a call whose
-         * stream is longer than its room retries with that much room */
-        if (lzo_mi355x_launch_decoded_length(d, dh.src_off, dh.src_len, dh.plen, dh.pstatus,
-                                             (uint32_t)k, NULL, 0xFFFFFFFFu, s) != 0 ||
-            hipMemcpyAsync(hh.plen, dh.plen, (size_t)k * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return;
-    }
-    for (int i = 0; i < k; i++) {
-        struct sc_req *r = g[i];
-        if (over && hh.status[i] == LZO_E_OUTPUT_OVERRUN && hh.plen[i] > r->room) {
-            r->produced = hh.plen[i];
-            r->rc = 1;
-            continue;
-        }
-        const size_t n = hh.out_len[i] < r->room ? hh.out_len[i] : r->room;
-        if (n)
-            memcpy(r->dst, h + o_out[i], n);
-        r->produced = hh.out_len[i];
-        r->rc = hh.status[i];
-    }
-    if (trace)
-        fprintf(stderr, "pom single-call group: kind %d, %d calls, %.3f ms\n", (int)kind, k, now_ms() - t0);
-}
-
-static int single_call(enum sc_kind kind, const uint8_t *src, size_t src_len, uint8_t *dst,
-                       size_t room, size_t *produced)
-{
-    int dev = 0;
-    if (src_len > 0xFFFFFFF0u || room > 0xFFFFFFF0u || lzo_mi355x_device_count() <= 0 ||
-        hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev)
-        return LZO_E_ERROR;
-    struct sc_req r = {kind, src, src_len, dst, room, 0, LZO_E_ERROR, 0, 0, NULL};
-    if (!sc_combine()) {
-        struct sc_req *g = &r;
-        sc_run_group(&g, 1, NULL);
-        *produced = r.produced;
-        return r.rc;
-    }
-    pthread_once(&sc_once, sc_init);
-    struct sc_queue *q = &sc_q[dev];
-    pthread_mutex_lock(&q->mu);
-    if (q->tail)
-        q->tail->next = &r;
-    else
-        q->head = &r;
-    q->tail = &r;
-    if (q->leader)
-        pthread_cond_broadcast(&q->cv);         /* (a leader may be waiting for company) */
-    while (!r.done) {
-        if (q->leader) {
-            pthread_cond_wait(&q->cv, &q->mu);
-            continue;
-        }
-        /* lead: the queue's oldest calls of the oldest call's kind.  When this
-         * thread's previous call was in the last group and that group had
-         * company, the other callers are probably between two calls: give
-         * them ~50 us to queue.  (A thread that was not in it -- a lone caller
-         * after a burst of others -- does not wait: ADVICE round 3.) */
-        q->leader = 1;
-        if (q->last_k > 1 && q->head == q->tail && sc_last_group[dev] == q->seq) {
-            struct timespec ts;
-            clock_gettime(CLOCK_MONOTONIC, &ts);
-            ts.tv_nsec += 50000;
-            if (ts.tv_nsec >= 1000000000L) {
-                ts.tv_sec++;
-                ts.tv_nsec -= 1000000000L;
-            }
-            pthread_cond_timedwait(&q->cv, &q->mu, &ts);
-        }
-        struct sc_req *g[kScGroup];
-        int k = 0;
-        size_t bytes = 0;
-        const enum sc_kind gk = q->head->kind;
-        struct sc_req **pp = &q->head, *prev = NULL;
-        while (*pp && k < kScGroup) {
-            struct sc_req *x = *pp;
-            const size_t xb = x->room + x->src_len;
-            if (x->kind != gk || (k > 0 && bytes + xb > kScGroupBytes)) {
-                prev = x;
-                pp = &x->next;
-                continue;
-            }
-            *pp = x->next;
-            if (q->tail == x)
-                q->tail = prev;
-            x->next = NULL;
-            g[k++] = x;
-            bytes += xb;
-        }
-        pthread_mutex_unlock(&q->mu);
-        sc_run_group(g, k, q);
-        pthread_mutex_lock(&q->mu);
-        q->seq++;
-        for (int i = 0; i < k; i++) {
-            g[i]->done = 1;
-            g[i]->group = q->seq;
-        }
-        q->leader = 0;
-        q->last_k = k;
-        pthread_cond_broadcast(&q->cv);
-    }
-    pthread_mutex_unlock(&q->mu);
-    sc_last_group[dev] = r.group;
-    *produced = r.produced;
-    return r.rc;
-}
-
-/* lib/minilzo.c:3159-3207.  The output is the reference's with a zero-filled
- * wrkmem (SURVEY.md finding 3), so wrkmem is not read. */
-int lzo1x_1_compress(const lzo_bytep src, lzo_uint src_len, lzo_bytep dst, lzo_uintp dst_len,
-                     lzo_voidp wrkmem)
-{
-    (void)wrkmem;
-    size_t n = 0;
-    const int rc = single_call(SC_COMPRESS, src, src_len, dst,
-                               lzo_mi355x_worst_compress(src_len), &n);
-    if (rc != LZO_E_ERROR)
-        *dst_len = n;
-    return rc;
-}
-
-/* lib/minilzo.c:3703-4190: *dst_len is the capacity in, the produced length out. */
-int lzo1x_decompress_safe(const lzo_bytep src, lzo_uint src_len, lzo_bytep dst,
-                          lzo_uintp dst_len, lzo_voidp wrkmem)
-{
-    (void)wrkmem;
-    size_t n = 0;
-    const int rc = single_call(SC_SAFE, src, src_len, dst, *dst_len, &n);
-    if (rc != LZO_E_ERROR)
-        *dst_len = n;
-    return rc;
-}
-
-/* GPU pre-scan of one host-resident stream: decoded length and status. */
-int lzo_mi355x_decoded_length(const uint8_t *src, unsigned long src_len, unsigned long *dst_len)
-{
-    struct slot *t = single_slot();
-    if (!t || src_len > 0xFFFFFFF0u)
-        return LZO_E_ERROR;
-    const size_t o_src = sc_hdr_bytes(1);
-    if (slot_reserve(t, o_src + src_len + 16, o_src + src_len + 16) != 0)
-        return LZO_E_ERROR;
-    uint8_t *h = t->hmem, *d = t->dmem;
-    hipStream_t s = t->stream;
-    struct sc_hdr hh = sc_hdr_at(h, 1), dh = sc_hdr_at(d, 1);
-    memset(h, 0, o_src);
-    hh.src_off[0] = o_src;
-    hh.src_len[0] = (uint32_t)src_len;
-    if (src_len)
-        memcpy(h + o_src, src, src_len);
-    if (hipMemcpyAsync(d, h, o_src + src_len, hipMemcpyHostToDevice, s) != hipSuccess ||
-        lzo_mi355x_launch_decoded_length(d, dh.src_off, dh.src_len, dh.plen, dh.pstatus, 1, NULL,
-                                         0xFFFFFFFFu, s) != 0 ||
-        hipMemcpyAsync(h, d, o_src, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return LZO_E_ERROR;
-    *dst_len = hh.plen[0];
-    return hh.pstatus[0];
-}
-
-/* The unchecked decoder (lib/minilzo.c:3308-3699) that mds/itb.c:2964,
- * mdsl/gc.c:770 and api/api.c:6438 call.  It never learns the destination
- * size (mds/itb.c:2951-2964 passes an uninitialised *out_len): the GPU
- * decodes into a guessed room (16x the input, at least 256 KiB) and the
- * output comes back with its length in one round trip; only a block that
- * decodes to more than that takes a length pre-scan and a second decode. */
-int lzo1x_decompress(const lzo_bytep src, lzo_uint src_len, lzo_bytep dst, lzo_uintp dst_len,
-                     lzo_voidp wrkmem)
-{
-    (void)wrkmem;
-    size_t room = (size_t)src_len * 16;
-    if (room < ((size_t)256 << 10))
-        room = (size_t)256 << 10;
-    if (room > 0xFFFFFFF0u)
-        room = 0xFFFFFFF0u;
-    size_t n = 0;
-    int rc = single_call(SC_UNCHECKED, src, src_len, dst, room, &n);
-    if (rc == 1)                                   /* longer than the guess */
-        rc = single_call(SC_UNCHECKED, src, src_len, dst, n, &n);
-    if (rc != LZO_E_ERROR)
-        *dst_len = n;
-    return rc;
 }

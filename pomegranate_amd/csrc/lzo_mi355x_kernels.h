@@ -8,6 +8,8 @@
 #include <stdint.h>
 #include <hip/hip_runtime_api.h>
 
+#include "host_debug.h"         /* the debug switches the launchers read */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -126,11 +128,6 @@ int lzo_mi355x_launch_decoded_length(const uint8_t *src, const uint64_t *src_off
                                      const uint32_t *src_len, uint32_t *out_len,
                                      int32_t *status, uint32_t nblocks, uint32_t *cap_out,
                                      uint32_t cap_limit, hipStream_t stream);
-
-/* Host side (lzo_host.c), not part of the ABI: the debug switches of
- * POM_LZO_DEBUG ("key=value,..."; NULL / dflt when the key is absent). */
-const char *pom_dbg_str(const char *key, char *buf, size_t n);
-long pom_dbg_int(const char *key, long dflt);
 
 /* Host side (lzo_host.c), not part of the ABI: lzo_mi355x_compress_batch
  * with on_chunk(ctx, ids, nb) called as each chunk's blocks are delivered

@@ -10,6 +10,9 @@
  *   - the H2D span [0, o_dst) holds exactly the uploaded fields (but for
  *     alignment padding);
  *   - the result D2H span is exactly the union of the operation's result fields.
+ * The same rules hold for the staging of the single calls' groups
+ * (pom_layout_single) of 1 to 64 calls, whose inputs and outputs are each
+ * 256-byte aligned and whose only D2H span is the pre-scan's.
  * Prints the number of layouts checked; exits non-zero at the first failure. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -190,8 +193,63 @@ static void walk_case(const char *name, const struct walk_spec *W, const size_t 
     check(&L, K->res_off, K->res_bytes);
 }
 
+/* A group of k single calls: call i has the a + i-th size as input, the c + 2i-th as room. */
+static const size_t kScSizes[] = {0, 1, 255, 256, 257, (3u << 20) + 5, 5u << 20};
+
+static void single_case(size_t k, size_t a, size_t c)
+{
+    const size_t ns = sizeof kScSizes / sizeof kScSizes[0];
+    size_t src_len[64], room[64], o_src[64], o_out[64];
+    for (size_t i = 0; i < k; i++) {
+        src_len[i] = kScSizes[(a + i) % ns];
+        room[i] = kScSizes[(c + 2 * i) % ns];
+    }
+    struct single_layout S;
+    what = "single calls";
+    nR = 0;
+    pom_layout_single(&S, k, src_len, room, o_src, o_out);
+    /* the header is ALIGN_UP(44k + 4, 256); inputs, then outputs, one behind the other, each 256-aligned */
+    size_t at = POM_ALIGN_UP(44 * k + 4, 256);
+    if (S.o_src != at)
+        fail("the header is not 44k + 4 bytes, rounded up to 256", NULL, NULL);
+    for (size_t i = 0; i < k; i++) {
+        if (o_src[i] != at || at % 256)
+            fail("an input is out of place", NULL, NULL);
+        at += POM_ALIGN_UP(src_len[i], 256);
+    }
+    if (S.o_dst != at || S.dtotal != at)
+        fail("the H2D span or the device side does not end with the inputs", NULL, NULL);
+    for (size_t i = 0; i < k; i++) {
+        if (o_out[i] != at || at % 256)
+            fail("an output is out of place", NULL, NULL);
+        at += POM_ALIGN_UP(room[i], 256);
+    }
+    if (S.htotal != at)
+        fail("the host side does not end with the outputs", NULL, NULL);
+    /* out_len and status go up with the header (zero and -1) and are read on the
+     * host side, where the kernels write them: no D2H but the pre-scan's */
+    add("src_off", S.o_srcoff, 8, 8 * k, BOTH, UPLOAD);
+    add("dst_off", S.o_dstoff, 8, 8 * k, BOTH, UPLOAD);
+    add("src_len", S.o_srclen, 4, 4 * k, BOTH, UPLOAD);
+    add("dst_cap", S.o_dstcap, 4, 4 * k, BOTH, UPLOAD);
+    add("out_len", S.o_outlen, 4, 4 * k, BOTH, UPLOAD);
+    add("status", S.o_status, 4, 4 * k, BOTH, UPLOAD);
+    add("plen", S.o_plen, 4, 4 * k, BOTH, RESULT);
+    add("pstatus", S.o_pstatus, 4, 4 * k, BOTH, RESULT);
+    add("fallback list", S.o_fb, 4, 4 * (1 + k), BOTH, UPLOAD);
+    add("inputs", S.o_src, 1, S.o_dst - S.o_src, BOTH, UPLOAD);
+    add("outputs", S.o_dst, 1, S.htotal - S.o_dst, HOST, PLAIN);
+    const struct layout L = {.o_dst = S.o_dst, .htotal = S.htotal, .dtotal = S.dtotal};
+    check(&L, S.pre_off, S.pre_bytes);
+}
+
 int main(void)
 {
+    static const size_t kScK[] = {1, 2, 8, 9, 63, 64};
+    for (size_t n = 0; n < sizeof kScK / sizeof kScK[0]; n++)
+        for (size_t a = 0; a < sizeof kScSizes / sizeof kScSizes[0]; a++)
+            for (size_t c = 0; c < sizeof kScSizes / sizeof kScSizes[0]; c++)
+                single_case(kScK[n], a, c);
     static const size_t kNb[] = {1, 2, 5};
     const size_t ns = sizeof kSizes / sizeof kSizes[0];
     size_t ids[5], src_len[8], cap[8];

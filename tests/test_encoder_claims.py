@@ -170,7 +170,7 @@ def cases(oracle):
 @pytest.fixture
 def debug_env(monkeypatch):
     def set_(value):
-        monkeypatch.setenv("POM_LZO_DEBUG", value)      # (lzo_host.c pom_dbg_str)
+        monkeypatch.setenv("POM_LZO_DEBUG", value)      # (host_debug.c pom_dbg_str)
         lzo.debug_reload()
     yield set_
     monkeypatch.delenv("POM_LZO_DEBUG", raising=False)

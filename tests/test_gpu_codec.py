@@ -217,7 +217,7 @@ def test_unchecked_decompress_codes(dev, unchecked):
 def test_single_calls_from_many_threads(dev, oracle):
     """Single calls arriving together from several threads (the MDS commit and
     service threads, mds/txg.c:1010-1011, mds/itb.c:2964) are combined into
-    shared launches (lzo_host.c single_call); every caller still gets exactly
+    shared launches (single_queue.c, host_single.c); every caller still gets exactly
     its own bytes, length and return code, whatever else shares its launch."""
     from concurrent.futures import ThreadPoolExecutor
     sizes = [12416, 65536, 100, 300000, 4096, 1, 70000, 536192] * 4
@@ -691,7 +691,7 @@ def test_encoder_kernels_vs_oracle(dev, gu, oracle, kernel, monkeypatch):
     per block, LDS dictionary) byte-identical to the oracle on the sweep's
     content models, sizes up to 300 KB, more blocks than one grid holds."""
     waves = "enc_waves=2" if kernel == "gdict_two_wave" else "enc_waves=1"
-    monkeypatch.setenv("POM_LZO_DEBUG", waves)          # (lzo_host.c pom_dbg_str)
+    monkeypatch.setenv("POM_LZO_DEBUG", waves)          # (host_debug.c pom_dbg_str)
     lzo.debug_reload()
     blocks = _sweep_blocks(300, 91)
     src = gu.device_batch(torch, blocks, dev, shift=1)
@@ -919,7 +919,7 @@ def test_latency_decoder_hands_over_malformed_and_short_room(dev, gu, malformed,
 
 def test_lone_single_calls_on_the_latency_decoder(dev, oracle):
     """Lone lzo1x_decompress / lzo1x_decompress_safe calls of 2 KB or more of
-    compressed input take the latency decoder (lzo_host.c lat_group): exact
+    compressed input take the latency decoder (host_ctx.c pom_lat_decode): exact
     bytes and lengths from 8 KB to 536,192 B, OUTPUT_OVERRUN for a room one
     byte short and for no room at all, and a malformed stream's code from the
     exact decoder behind it, as the reference (lib/minilzo.c:3703-4190)."""
@@ -976,7 +976,7 @@ def test_latency_decoder_zero_runs_stay_linear(dev, oracle):
 @pytest.mark.parametrize("k", [1, 3, 8])
 def test_small_host_batches_on_the_latency_decoder(dev, oracle, malformed, k):
     """Host batches of up to 8 blocks of 2 KB or more of compressed input
-    decode on one latency-decoder pipeline (lzo_host.c lat_chunk) with the
+    decode on one latency-decoder pipeline (host_ctx.c pom_lat_decode) with the
     exact decoder behind it: exact bytes, a block one byte short of room
     (OUTPUT_OVERRUN) and a malformed stream's reference code in the same
     batch."""
@@ -1002,7 +1002,7 @@ def test_small_host_batches_on_the_latency_decoder(dev, oracle, malformed, k):
 
 def test_latency_scratch_is_shared_across_threads(dev, oracle):
     """16 threads issuing 8-block host batches (each one latency-decoder
-    pipeline, lzo_host.c lat_chunk) share ONE latency scratch per device
+    pipeline, host_ctx.c pom_lat_decode) share ONE latency scratch per device
     (lat_acquire): the device memory they leave allocated stays near one
     scratch plus the threads' staging, where per-thread scratches (round 3)
     would hold 16 of them.  Every batch still decodes exactly."""
@@ -1038,3 +1038,99 @@ def test_latency_scratch_is_shared_across_threads(dev, oracle):
     staging = 16 * 4 * (int(zl.sum()) + int(cp.sum()) + (1 << 20))   # each thread's chunk staging, generously
     assert held <= 2 * need + staging, (held, need, staging)
     assert held < 16 * need, (held, need)
+
+
+# ---------------------------------------------------------------------------
+# The single calls' and the host batches' paths under the debug keys that
+# select them (host_single.c, host_ctx.c pom_lat_decode)
+# ---------------------------------------------------------------------------
+@pytest.fixture
+def debug_env(monkeypatch):
+    def set_(value):
+        monkeypatch.setenv("POM_LZO_DEBUG", value)      # (host_debug.c pom_dbg_str)
+        lzo.debug_reload()
+    yield set_
+    monkeypatch.delenv("POM_LZO_DEBUG", raising=False)
+    lzo.debug_reload()
+
+
+@pytest.fixture(scope="module")
+def single_fx(oracle):
+    """ITB blocks of 1, 100, 4,096 and 65,536 bytes with their oracle streams
+    (only the last is 2 KiB or more: the latency decoder's), and 300,000 zero
+    bytes, whose ~1.2 KB stream decodes past lzo1x_decompress's first guess of
+    256 KiB."""
+    blocks = [synth.block(synth.ITB, 7300 + i, n) for i, n in enumerate((1, 100, 4096, 65536))]
+    comps = [oracle.compress(b) for b in blocks]
+    assert [len(z) >= 2048 for z in comps] == [False, False, False, True]
+    zeros = bytes(300000)
+    zz = oracle.compress(zeros)
+    assert len(zz) < 2048 and 16 * len(zz) < (256 << 10) < len(zeros)
+    return blocks, comps, zeros, zz
+
+
+def _decoded_length(z):
+    lib = lzo.load()
+    need = ctypes.c_ulong(0)
+    rc = lib.lzo_mi355x_decoded_length(ctypes.c_char_p(z), len(z), ctypes.byref(need))
+    return rc, need.value
+
+
+@pytest.mark.parametrize("debug", ["", "sc_combine=0", "sc_lat=0", "sc_lat_min=1"])
+def test_single_calls_under_debug_settings(dev, debug_env, single_fx, debug):
+    """Every minilzo.h single call through the combining queue and without it
+    (sc_combine=0), with the latency decoder at its default threshold, off
+    (sc_lat=0: the windowed decoder alone) and on for every block
+    (sc_lat_min=1): compress equals the oracle; both decoders return the
+    block; a room one byte short is LZO_E_OUTPUT_OVERRUN;
+    lzo_mi355x_decoded_length returns the block's length; and 300,000 zero
+    bytes take the pre-scan and the second round trip and come back exact."""
+    blocks, comps, zeros, zz = single_fx
+    debug_env(debug)
+    for d, z in zip(blocks, comps):
+        rc, got = lzo.lzo1x_1_compress(d)
+        assert rc == 0 and got == z, len(d)
+        rc, back = lzo.lzo1x_decompress(z)
+        assert rc == 0 and back == d, len(d)
+        rc, back = lzo.lzo1x_decompress_safe(z, len(d))
+        assert rc == 0 and back == d, len(d)
+        rc, _ = lzo.lzo1x_decompress_safe(z, len(d) - 1)
+        assert rc == lzo.LZO_E_OUTPUT_OVERRUN, len(d)
+        assert _decoded_length(z) == (0, len(d))
+    rc, back = lzo.lzo1x_decompress(zz)
+    assert rc == 0 and back == zeros
+
+
+@pytest.fixture(scope="module")
+def lat_limit_fx(oracle):
+    """Nine ITB/TEXT blocks whose streams are 2 KiB or more, and one whose
+    stream is shorter, with what the oracle decodes them to."""
+    blocks = [synth.block(synth.ITB if i % 2 else synth.TEXT, 7400 + i, 24000 + 1000 * i) for i in range(9)]
+    small = synth.block(synth.ITB, 7410, 1000)
+    comps = [oracle.compress(b) for b in blocks]
+    zsmall = oracle.compress(small)
+    assert all(len(z) >= 2048 for z in comps) and len(zsmall) < 2048
+    return blocks, comps, small, zsmall
+
+
+@pytest.mark.parametrize("case", ["eight", "nine", "eight_one_short_stream"])
+def test_host_batches_around_the_latency_limit(dev, oracle, lat_limit_fx, case):
+    """Decode batches at the edge of the latency decoder's range (at most 8
+    blocks, each of 2,048 or more compressed bytes): 8 eligible streams (the
+    latency pipeline), 9 (the throughput decoders), and 8 of which one is
+    under 2,048 compressed bytes (the throughput decoders).  Each gives the
+    oracle's codes and bytes."""
+    blocks, comps, small, zsmall = lat_limit_fx
+    if case == "eight":
+        zs, ds = comps[:8], blocks[:8]
+    elif case == "nine":
+        zs, ds = comps, blocks
+    else:
+        zs, ds = comps[:5] + [zsmall] + comps[5:7], blocks[:5] + [small] + blocks[5:7]
+    caps = [len(d) for d in ds]
+    want = [oracle.decompress_safe(z, c) for z, c in zip(zs, caps)]
+    assert want == [(0, d) for d in ds]
+    rc, status, outs = lzo.decompress_batch(zs, caps)
+    assert rc == 0
+    assert status == [w[0] for w in want]
+    assert outs == [w[1] for w in want]

@@ -39,7 +39,7 @@ def _needs_gpu(dev):
 @pytest.fixture
 def debug_env(monkeypatch):
     def set_(value):
-        monkeypatch.setenv("POM_LZO_DEBUG", value)      # (lzo_host.c pom_dbg_str)
+        monkeypatch.setenv("POM_LZO_DEBUG", value)      # (host_debug.c pom_dbg_str)
         lzo.debug_reload()
     yield set_
     monkeypatch.delenv("POM_LZO_DEBUG", raising=False)
