@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "col_slice.h"
+#include "host_requests.h"
 #include "lzo_mi355x.h"
 #include "lzo_mi355x_kernels.h"
 #include "minilzo.h"
@@ -200,7 +201,8 @@ int pom_col_read_batch(const uint8_t *const *zip, const size_t *zip_len, size_t 
     if (nreq == 0)
         return LZO_E_OK;
     size_t *slot = malloc((ncol + 1) * sizeof(*slot));       /* column -> k, or a code below */
-    size_t *first = calloc(ncol + 2, sizeof(*first));
+    size_t *key = malloc(nreq * sizeof(*key));               /* request -> k, or none */
+    size_t *first = malloc((ncol + 2) * sizeof(*first));
     size_t *fill = malloc((ncol + 1) * sizeof(*fill));
     size_t *ids = malloc(nreq * sizeof(*ids));
     const uint8_t **src = malloc((ncol + 1) * sizeof(*src));
@@ -208,7 +210,7 @@ int pom_col_read_batch(const uint8_t *const *zip, const size_t *zip_len, size_t 
     uint64_t *want = malloc((ncol + 1) * sizeof(*want));
     int32_t *st = malloc((ncol + 1) * sizeof(*st));
     int rc = LZO_E_OUT_OF_MEMORY;
-    if (!slot || !first || !fill || !ids || !src || !slen || !want || !st)
+    if (!slot || !key || !first || !fill || !ids || !src || !slen || !want || !st)
         goto out;
     const size_t kUnused = (size_t)-1, kNoHeader = (size_t)-2, kRefused = (size_t)-3;
     for (size_t c = 0; c < ncol; c++)
@@ -234,13 +236,11 @@ int pom_col_read_batch(const uint8_t *const *zip, const size_t *zip_len, size_t 
             m++;
         }
     }
-    size_t ngpu = 0;
     for (size_t r = 0; r < nreq; r++) {
         const size_t c = req[r].col;
-        if (c < ncol && slot[c] < m) {
-            first[slot[c] + 1]++;
+        key[r] = c < ncol ? slot[c] : kUnused;
+        if (key[r] < m) {
             err[r] = LZO_E_ERROR;               /* until its chunk delivers */
-            ngpu++;
         } else {
             uint64_t n;
             err[r] = col_slice_decide(c < ncol, c < ncol && slot[c] != kNoHeader, LZO_E_ERROR, 0, 0,
@@ -248,17 +248,8 @@ int pom_col_read_batch(const uint8_t *const *zip, const size_t *zip_len, size_t 
         }
     }
     rc = LZO_E_OK;
-    if (ngpu == 0)
+    if (pom_group_requests(key, nreq, m, first, ids) == 0)
         goto out;
-    for (size_t k = 0; k < m; k++) {
-        first[k + 1] += first[k];
-        fill[k] = first[k];
-    }
-    for (size_t r = 0; r < nreq; r++) {
-        const size_t c = req[r].col;
-        if (c < ncol && slot[c] < m)
-            ids[fill[slot[c]]++] = r;
-    }
     struct pom_col_sink C = {want, first, ids, req, out, out_len, err, st, 0};
     rc = pom_col_read_chunked(src, slen, m, &C);
     if (rc != LZO_E_OK)
@@ -287,6 +278,7 @@ int pom_col_read_batch(const uint8_t *const *zip, const size_t *zip_len, size_t 
     }
 out:
     free(slot);
+    free(key);
     free(first);
     free(fill);
     free(ids);

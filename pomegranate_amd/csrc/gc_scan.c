@@ -1,8 +1,8 @@
 /*
  * gc_scan.c -- the MDSL garbage collector's data scan (include/pom_gc.h): per
  * ITB the decode switch and the bitmap walk of mdsl_gc_data_round
- * (mdsl/gc.c:945-993), batched.  The header checks and the reassembly are
- * here, and with them the front and back halves the three walks' batches share
+ * (mdsl/gc.c:945-993), batched.  The reassembly is here (the header checks
+ * are host_requests.c's pom_itb_walk_header), and with it the front and back halves the three walks' batches share
  * (pom_walk_begin, pom_walk_finish); the chunks -- compressed payloads up, the
  * decoders, the walk (itb_scan.hip), counts and ranges back -- go through the
  * host batches' pipeline (host_records.c, gc_ops).
@@ -11,48 +11,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "host_requests.h"
 #include "lzo_mi355x.h"
 #include "lzo_mi355x_kernels.h"
 #include "minilzo.h"
 #include "pom_gc.h"
 #include "pom_kvlist.h"
 #include "pom_itb.h"
-
-static uint32_t rd32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-static uint16_t rd16(const uint8_t *p)
-{
-    uint16_t v;
-    memcpy(&v, p, 2);
-    return v;
-}
-
-int pom_itb_walk_header(const uint8_t *rec, size_t rec_len, struct pom_walk_block *w)
-{
-    if (rec_len < POM_ITBH_SIZE)
-        return -EINVAL;
-    const uint32_t len = rd32(rec + POM_ITBH_LEN_OFF), zlen = rd32(rec + POM_ITBH_ZLEN_OFF);
-    const uint16_t algo = rd16(rec + POM_ITBH_ALGO_OFF);
-    const uint8_t ad = rec[POM_ITBH_ADEPTH_OFF];
-    if (len < POM_ITBH_SIZE || len > rec_len || (algo != POM_COMPR_NONE && algo != POM_COMPR_LZO) ||
-        ad == 0 || ad > POM_ITB_ADEPTH_MAX)
-        return -EINVAL;
-    if (algo == POM_COMPR_LZO &&
-        (zlen <= POM_ITBH_SIZE || zlen - POM_ITBH_SIZE > POM_ITB_PAYLOAD_MAX))
-        return -EINVAL;
-    w->src = rec + POM_ITBH_SIZE;
-    w->src_len = len - POM_ITBH_SIZE;
-    w->is_lzo = algo == POM_COMPR_LZO;
-    w->cap = w->is_lzo ? zlen - POM_ITBH_SIZE : 0;
-    w->adepth = ad;
-    w->entries = (int32_t)rd32(rec + POM_ITBH_ENTRIES_OFF);
-    return 0;
-}
 
 int pom_walk_begin(struct pom_walk_batch *W, const uint8_t *const *rec, const size_t *rec_len, size_t n,
                    const struct pom_walk_out *O)
@@ -169,7 +134,7 @@ int pom_walk_finish(struct pom_walk_batch *W, int rc, const struct pom_walk_out 
     }
     rc = !O->count_only && total > O->out_cap ? POM_GC_E_NOSPACE : LZO_E_OK;
 out:
-    pom_walk_sink_free(&W->G);
+    pom_walk_bufs_free(&W->G.bufs);
     pthread_mutex_destroy(&W->G.mu);
     free(W->idx);
     free(W->src);

@@ -6,9 +6,7 @@
 
 #include "host_layout.h"
 #include "pom_column.h"
-#include "pom_kvget.h"
 #include "pom_kvlist.h"
-#include "pom_lookup.h"
 
 size_t pom_walk_max_ites(size_t n)
 {
@@ -161,18 +159,20 @@ void pom_layout_col(struct layout *L, const size_t *ids, size_t nb, const size_t
     L->dtotal = o;
 }
 
-void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
-                       const size_t *cap, size_t nreq, size_t names_bytes, size_t scratch)
+void pom_layout_req(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                    const size_t *cap, const struct req_spec *Q, size_t nreq, size_t blob_bytes, int records,
+                    size_t scratch)
 {
-    size_t in, out, o = 0, r = 0;
+    size_t in, out, o = 0, r = Q->rec_max ? 8 : 0;
     layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
-    struct lookup_layout *K = &L->u.lk;
+    struct req_layout *K = &L->u.req;
     K->nreq = nreq;
-    K->names_bytes = names_bytes;
+    K->blob_bytes = blob_bytes;
+    K->rcap = records ? POM_ALIGN_UP(Q->rec_max * nreq, 16) : 0;
     L->o_srcoff = take(&o, 8 * nb);
     L->o_dstoff = take(&o, 8 * nb);
     K->scan.o_scanoff = take(&o, 8 * nb);
-    K->o_req = take(&o, sizeof(struct pom_lookup_req) * nreq);
+    K->o_req = take(&o, POM_REQ_SIZE * nreq);
     L->o_srclen = take(&o, 4 * nb);
     L->o_dstcap = take(&o, 4 * nb);
     L->o_status = take(&o, 4 * nb);
@@ -180,55 +180,20 @@ void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nl
     K->scan.o_adepth = take(&o, nb);
     o = POM_ALIGN_UP(o, 256);
     L->o_src = take(&o, in);
-    K->o_names = take(&o, POM_ALIGN_UP(names_bytes, 256));
+    K->o_blob = take(&o, POM_ALIGN_UP(blob_bytes, 256));
     L->o_dst = o;
-    K->r_err = take(&r, 4 * nreq);
-    K->r_nr = take(&r, 4 * nreq);
-    K->r_depth = take(&r, 4 * nreq);
+    for (size_t w = 0; w < Q->nwords; w++)
+        K->r_word[w] = take(&r, 4 * nreq);
+    r = POM_ALIGN_UP(r, 8);
+    K->r_lease = take(&r, Q->lease ? 8 * nreq : 0);
     K->res_hdr = POM_ALIGN_UP(r, 16);
-    K->res_bytes = K->res_hdr + POM_LK_REC_SIZE * nreq;
-    K->o_hres = o;
-    L->htotal = o + K->res_bytes;
-    o += out;
-    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
-    K->o_res = take(&o, K->res_bytes);
-    L->dtotal = o;
-}
-
-void pom_layout_kvget(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
-                      const size_t *cap, size_t nreq, size_t keys_bytes, int records, size_t scratch)
-{
-    size_t in, out, o = 0, r = 8;
-    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
-    struct kvget_layout *K = &L->u.kg;
-    K->nreq = nreq;
-    K->keys_bytes = keys_bytes;
-    K->rcap = records ? POM_ALIGN_UP(POM_KG_REC_MAX * nreq, 16) : 0;
-    L->o_srcoff = take(&o, 8 * nb);
-    L->o_dstoff = take(&o, 8 * nb);
-    K->scan.o_scanoff = take(&o, 8 * nb);
-    K->o_req = take(&o, sizeof(struct pom_kvget_req) * nreq);
-    L->o_srclen = take(&o, 4 * nb);
-    L->o_dstcap = take(&o, 4 * nb);
-    L->o_status = take(&o, 4 * nb);
-    L->o_outlen = take(&o, 4 * nb);
-    K->scan.o_adepth = take(&o, nb);
-    o = POM_ALIGN_UP(o, 256);
-    L->o_src = take(&o, in);
-    K->o_keys = take(&o, POM_ALIGN_UP(keys_bytes, 256));
-    L->o_dst = o;
-    K->r_err = take(&r, 4 * nreq);
-    K->r_nr = take(&r, 4 * nreq);
-    K->r_depth = take(&r, 4 * nreq);
-    K->r_len = take(&r, 4 * nreq);
-    K->r_lease = take(&r, 8 * nreq);
-    K->res_bytes = r;
+    K->res_bytes = Q->rec_fixed ? K->res_hdr + Q->rec_fixed * nreq : r;
     K->o_hres = o;
     K->o_hrec = POM_ALIGN_UP(o + K->res_bytes, 16);
     L->htotal = K->o_hrec + K->rcap;
     o += out;
     L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
-    K->o_first = take(&o, 8 * nreq);
+    K->o_first = take(&o, Q->rec_max ? 8 * nreq : 0);
     K->o_res = take(&o, POM_ALIGN_UP(K->res_bytes, 256));
     K->o_pack = take(&o, K->rcap);
     L->dtotal = o;

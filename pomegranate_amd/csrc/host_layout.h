@@ -79,32 +79,43 @@ struct col_layout {
     size_t res_hdr, res_bytes;  /* the slices start at res_hdr; the whole is res_bytes */
 };
 
-/* Lookups.  As col_layout: a header of three arrays, then the 136-byte records. */
-struct lookup_layout {
-    struct scan_layout scan;
-    size_t nreq, names_bytes;
-    size_t o_req;               /* struct pom_lookup_req per request */
-    size_t o_names;             /* the chunk's own name blob, behind the inputs */
-    size_t o_res, o_hres;
-    size_t r_err, r_nr, r_depth;    /* i32, u32, u32 per request */
-    size_t res_hdr, res_bytes;
+/* The request operations: lookups and key/value gets.  A kind is told by where
+ * its 32-byte request keeps its ITB number, its offset into the call's blob
+ * (names, keys) and the length it reads there, by the rule that refuses a
+ * request its blob bytes, and by its results: the first nwords of enum
+ * req_word per request, a u64 lease, and records that are either rec_fixed
+ * bytes each or packed, of at most rec_max bytes each. */
+enum req_word { RW_ERR, RW_NR, RW_DEPTH, RW_LEN, RW_N };
+#define POM_REQ_SIZE 32u
+
+struct req_spec {
+    size_t o_itb, o_blob;       /* the request's u32 fields: its ITB, its offset into the blob */
+    size_t o_len, len_bytes;    /* its blob length: a u16 or u32 field; above len_max the request is refused */
+    uint32_t len_max;
+    size_t o_flag;              /* a u32 field that must have a bit of flag_mask set, else refused (mask 0: no such rule) */
+    uint32_t flag_mask;
+    size_t nwords;              /* err, nr, depth (lookup), len (get): i32, then u32 each */
+    int lease;                  /* a u64 per request behind the words */
+    size_t rec_fixed;           /* fixed records of this many bytes, behind the words in the same D2H span; or 0: */
+    size_t rec_max;             /* variable ones, packed on the device behind first[], at most this long */
 };
 
-/* Key/value gets.  The lookup's inputs with the key blob in the names' place.
- * The fixed-size results lie alike on both sides behind the chunk's record
- * total (on the device the last entry of first[]), and come back in one copy;
- * the packed records follow in a second one, sized by that total. */
-struct kvget_layout {
+/* The results -- the words, the lease, fixed records 16-byte aligned behind
+ * them -- lie alike on both sides (device o_res, host o_hres) and come back in
+ * one copy; the r_ offsets are relative to their start.  Variable records: the
+ * results start with the chunk's record total (on the device the last entry of
+ * first[]), and the packed records follow in a second copy sized by it. */
+struct req_layout {
     struct scan_layout scan;
-    size_t nreq, keys_bytes;
-    size_t o_req;               /* struct pom_kvget_req per request */
-    size_t o_keys;              /* the chunk's own key blob, behind the inputs */
-    size_t o_first;             /* device only: u64, nreq + 1; first[nreq] is the results' first word */
-    size_t o_res, o_hres;       /* [total u64][err][nr][depth][len][lease] */
-    size_t r_err, r_nr, r_depth, r_len;     /* i32, u32, u32, u32 per request */
+    size_t nreq, blob_bytes;
+    size_t o_req;               /* POM_REQ_SIZE per request */
+    size_t o_blob;              /* the chunk's own blob, behind the inputs */
+    size_t o_first;             /* device only, variable records: u64, nreq + 1; first[nreq] is the results' first word */
+    size_t o_res, o_hres;
+    size_t r_word[RW_N];        /* i32 or u32 per request */
     size_t r_lease;             /* u64 per request */
-    size_t res_bytes;
-    size_t rcap;                /* record room, in bytes: 364 a request (0: lengths only) */
+    size_t res_hdr, res_bytes;  /* fixed records start at res_hdr; the whole copy is res_bytes */
+    size_t rcap;                /* room for the variable records, in bytes (0: none come back) */
     size_t o_pack, o_hrec;      /* device, host: the packed records */
 };
 
@@ -125,8 +136,7 @@ struct layout {
         struct codec_layout codec;
         struct walk_layout walk;
         struct col_layout col;
-        struct lookup_layout lk;
-        struct kvget_layout kg;
+        struct req_layout req;
     } u;
 };
 
@@ -140,12 +150,10 @@ void pom_layout_walk(struct layout *L, const size_t *ids, size_t nb, size_t nlzo
 /* slice_bytes: the requests' clamped lengths, each rounded up to 16 */
 void pom_layout_col(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
                     const size_t *cap, size_t nreq, size_t slice_bytes, size_t scratch);
-void pom_layout_lookup(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
-                       const size_t *cap, size_t nreq, size_t names_bytes, size_t scratch);
-
-/* records != 0: room for every request's longest record on both sides */
-void pom_layout_kvget(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
-                      const size_t *cap, size_t nreq, size_t keys_bytes, int records, size_t scratch);
+/* records != 0: room for every request's longest variable record on both sides */
+void pom_layout_req(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                    const size_t *cap, const struct req_spec *Q, size_t nreq, size_t blob_bytes, int records,
+                    size_t scratch);
 
 /* The staging of a group of k single calls (host_single.c).  The header
  * arrays, then the inputs, lie alike on both sides and go up in one H2D copy

@@ -6,15 +6,17 @@
  * listing (itb_keys.hip) -- share one layout, one staging and one delivery,
  * told apart by their list of result words and their record unit; the column
  * read (col_slice.hip), the lookup (itb_find.hip) and the key/value get
- * (itb_kvget.hip) carry requests.  Their callers (gc_scan.c, readdir.c,
- * kvlist.c, column_codec.c, lookup.c, kvget.c) select
- * the blocks and put the results in the caller's order.
+ * (itb_kvget.hip) carry requests, the last two as one operation told apart by
+ * a descriptor (struct req_spec) and their kernels.  Their callers (gc_scan.c,
+ * readdir.c, kvlist.c, column_codec.c, lookup.c, kvget.c) select the blocks
+ * and put the results in the caller's order.
  */
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "host_pipeline.h"
+#include "host_requests.h"
 #include "lzo_mi355x.h"
 #include "minilzo.h"
 #include "pom_column.h"
@@ -55,6 +57,16 @@ static int results_back(struct slot *S, size_t o_hres, size_t o_res, size_t byte
     return 0;
 }
 
+/* A chunk's records join the call's buffers until the caller has placed them
+ * (the chunks of a multi-GPU batch finish on several threads). */
+static void keep_records(struct pom_walk_buf **bufs, pthread_mutex_t *mu, struct pom_walk_buf *buf)
+{
+    pthread_mutex_lock(mu);
+    buf->next = *bufs;
+    *bufs = buf;
+    pthread_mutex_unlock(mu);
+}
+
 /* ------------------------------------------------------------------------ */
 /* The walks: decode, walk, counts and records back                          */
 /* ------------------------------------------------------------------------ */
@@ -89,13 +101,6 @@ static const struct walk_spec rd_spec = {rd_words, sizeof rd_words, POM_DENT_HDR
 struct walk_call {
     struct pom_walk_sink *G;
     struct walk_spec spec;
-};
-
-/* A chunk's records, kept until the caller has placed them (pad: the records start 16-byte aligned). */
-struct pom_walk_buf {
-    struct pom_walk_buf *next;
-    uint64_t pad;
-    uint8_t bytes[];
 };
 
 /* The sink's array for each result word of the call, in the spec's order. */
@@ -272,20 +277,8 @@ static int walk_unpack(struct slot *S, const struct layout *L, const struct hbat
         pom_copy_jobs(jobs, L->nb);
         free(jobs);
     }
-    pthread_mutex_lock(&G->mu);
-    buf->next = G->bufs;
-    G->bufs = buf;
-    pthread_mutex_unlock(&G->mu);
+    keep_records(&G->bufs, &G->mu, buf);
     return 0;
-}
-
-void pom_walk_sink_free(struct pom_walk_sink *sink)
-{
-    while (sink->bufs) {
-        struct pom_walk_buf *next = sink->bufs->next;
-        free(sink->bufs);
-        sink->bufs = next;
-    }
 }
 
 static const struct chunk_ops gc_ops = {"gc scan", 0, walk_cap, NULL, walk_unreached, walk_layout,
@@ -481,103 +474,78 @@ int pom_col_read_chunked(const uint8_t *const *src, const size_t *src_len, size_
 }
 
 /* ------------------------------------------------------------------------ */
-/* Lookups: decode, chain walk (itb_find.hip), matched MDUs back              */
+/* Requests: decode, chain walk (itb_find.hip, itb_kvget.hip), results back   */
 /* ------------------------------------------------------------------------ */
 /* The walks' partition (LZO records first, stored ones walked as staged) with
  * the column reads' requests: an ITB and all its requests are in one chunk;
  * request j of the chunk is the j-th in block order, then in the block's own
- * order, renumbered to the chunk's ITB index, its name staged in a blob of the
- * chunk's own.  A request whose name the caller's blob does not hold, or whose
- * namelen is above 255, gets no name bytes and a name_off past the chunk's
- * blob: the kernel's rule 4 refuses it, behind rules 1 to 3 as everywhere.
- * Every result has a fixed size, so one copy of a known size brings them back,
- * queued once the chunk's kernels are done (the column reads say why).  The
- * decoder's status reaches the host through the requests' err.  Staging (host
- * and device alike up to the inputs' end; pom_layout_lookup):
+ * order, renumbered to the chunk's ITB index, its name or string key staged in
+ * a blob of the chunk's own.  A request the kind refuses (host_requests.h: a
+ * name or key the caller's blob does not hold, a namelen above 255, a get that
+ * is no string get or has sklen above 320) gets no blob bytes and an offset
+ * past the chunk's blob: where the kernel reads it, its rule 4 refuses it,
+ * behind rules 1 to 3 as everywhere.  The decoder's status reaches the host
+ * through the requests' err.  Fixed-size results come back in one copy of a
+ * known size, queued once the chunk's kernels are done (the column reads say
+ * why).  Variable-length records come back as the walks' do: the fixed-size
+ * results and the chunk's record total in one copy queued behind the kernels,
+ * exactly that many record bytes in a second one sized once the first is back.
+ * Staging (host and device alike up to the inputs' end; pom_layout_req):
  *   [src_off u64][dst_off u64][scan_off u64][requests, nreq][src_len u32][dst_cap u32]
  *   [status i32][out_len u32][adepth u8]
- *   [src bytes, 16-B aligned per block][names]
- *   device: [decoded payloads][decoder scratch]
- *   both:   [err i32, nreq][nr u32, nreq][depth u32, nreq][records, 136 * nreq]  <- D2H, one copy
+ *   [src bytes, 16-B aligned per block][blob]
+ *   device: [decoded payloads][decoder scratch][get: first u64, nreq]
+ *   both:   [the kind's results, nreq each]                          <- D2H, one copy
+ *           [get: the chunk's records, packed, unless lengths only]  <- D2H, sized after the first
+ * The results:
+ *   lookup  [err i32][nr u32][depth u32][records, 136 each]
+ *   get     [total u64][err i32][nr u32][depth u32][len u32][lease u64]; the total is first[nreq]
  * No other decoded byte leaves the device. */
-static int lk_name_ok(const struct pom_lookup_sink *K, const struct pom_lookup_req *q)
+struct req_call {
+    struct pom_req_sink *K;
+    pthread_mutex_t mu;             /* K->bufs: chunks of a multi-GPU batch finish on several threads */
+};
+
+static size_t req_cap(const struct hbatch *B, size_t b)
 {
-    return q->namelen <= 255 && (size_t)q->name_off + q->namelen <= K->names_len;
+    const struct req_call *C = B->sink;
+    return C->K->cap[b];
 }
 
-static size_t lk_name_bytes(const struct pom_lookup_sink *K, const struct pom_lookup_req *q)
+/* the chunk budget counts the requests, their blob bytes, their results and their records' room */
+static size_t req_extra_cost(const struct hbatch *B, size_t b)
 {
-    return lk_name_ok(K, q) ? q->namelen : 0;
+    const struct req_call *C = B->sink;
+    const struct req_spec *Q = C->K->spec;
+    size_t blob = 0;
+    const size_t nreq = pom_req_block(C->K, b, &blob);
+    return nreq * (POM_REQ_SIZE + 4 * Q->nwords + (Q->lease ? 8 : 0) + Q->rec_fixed +
+                   (Q->rec_max ? 8 + (C->K->records ? Q->rec_max : 0) : 0)) + blob;
 }
 
-static size_t lk_cap(const struct hbatch *B, size_t b)
+static void req_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
 {
-    const struct pom_lookup_sink *K = B->sink;
-    return K->cap[b];
+    const struct req_call *C = B->sink;
+    size_t nreq = 0, blob = 0;
+    for (size_t i = 0; i < nb; i++)
+        nreq += pom_req_block(C->K, ids[i], &blob);
+    pom_layout_req(L, ids, nb, nlzo, B->src_len, B->cap, C->K->spec, nreq, blob, C->K->records,
+                   lzo_mi355x_decompress_scratch((uint32_t)nlzo));
 }
 
-static size_t lk_names(const struct pom_lookup_sink *K, size_t b)
+static int req_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
 {
-    size_t n = 0;
-    for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++)
-        n += lk_name_bytes(K, &K->req[K->req_ids[k]]);
-    return n;
-}
-
-/* the chunk budget counts the requests, their names and their results (err, nr, depth, record) */
-static size_t lk_extra_cost(const struct hbatch *B, size_t b)
-{
-    const struct pom_lookup_sink *K = B->sink;
-    return (K->req_first[b + 1] - K->req_first[b]) *
-               (sizeof(struct pom_lookup_req) + 3 * sizeof(uint32_t) + POM_LK_REC_SIZE) + lk_names(K, b);
-}
-
-static void lk_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
-{
-    const struct pom_lookup_sink *K = B->sink;
-    size_t nreq = 0, names = 0;
-    for (size_t i = 0; i < nb; i++) {
-        nreq += K->req_first[ids[i] + 1] - K->req_first[ids[i]];
-        names += lk_names(K, ids[i]);
-    }
-    pom_layout_lookup(L, ids, nb, nlzo, B->src_len, B->cap, nreq, names,
-                      lzo_mi355x_decompress_scratch((uint32_t)nlzo));
-}
-
-static int lk_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
-{
-    const struct pom_lookup_sink *K = B->sink;
-    const struct lookup_layout *Y = &L->u.lk;
-    if (Y->nreq > 0xFFFFFFFFu || Y->names_bytes > 0xFFFFFFF0u)
+    const struct req_call *C = B->sink;
+    if (pom_req_stage(L, h, C->K) != 0)
         return -1;
-    struct pom_lookup_req *rq = (struct pom_lookup_req *)(h + Y->o_req);
-    uint8_t *nm = h + Y->o_names;
-    size_t j = 0, at = 0;
     pom_stage_inputs(L, h, B);
-    stage_scan(L, &Y->scan, h, K->adepth);
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
-            const struct pom_lookup_req *q = &K->req[K->req_ids[k]];
-            const size_t n = lk_name_bytes(K, q);
-            rq[j] = *q;
-            rq[j].itb = (uint32_t)i;            /* the chunk's own ITB index */
-            if (lk_name_ok(K, q)) {
-                rq[j].name_off = (uint32_t)at;
-                if (n)
-                    memcpy(nm + at, K->names + q->name_off, n);
-                at += n;
-            } else {
-                rq[j].name_off = 0xFFFFFFFFu;   /* outside the chunk's blob, as it was outside the caller's */
-            }
-        }
-    }
+    stage_scan(L, &L->u.req.scan, h, C->K->adepth);
     return 0;
 }
 
 static int lk_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
 {
-    const struct lookup_layout *Y = &L->u.lk;
+    const struct req_layout *Y = &L->u.req;
     uint8_t *d = S->dmem, *res = d + Y->o_res;
     (void)B;
     if (pom_decode_lzo_blocks(S, L, 0) != 0)
@@ -585,158 +553,14 @@ static int lk_kernels(struct slot *S, const struct layout *L, const struct hbatc
     return lzo_mi355x_launch_lookup(d, (const uint64_t *)(d + Y->scan.o_scanoff), (const uint32_t *)(d + L->o_outlen),
                                     (const int32_t *)(d + L->o_status), d + Y->scan.o_adepth, (uint32_t)L->nb,
                                     (const struct pom_lookup_req *)(d + Y->o_req), (uint32_t)Y->nreq,
-                                    d + Y->o_names, (uint32_t)Y->names_bytes, (int32_t *)(res + Y->r_err),
-                                    (uint32_t *)(res + Y->r_nr), (uint32_t *)(res + Y->r_depth), res + Y->res_hdr,
-                                    S->stream);
-}
-
-static int lk_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
-{
-    (void)B;
-    return results_back(S, L->u.lk.o_hres, L->u.lk.o_res, L->u.lk.res_bytes, packed);
-}
-
-/* The results go to their places in the caller's request order. */
-static int lk_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
-{
-    struct pom_lookup_sink *K = B->sink;
-    const struct lookup_layout *Y = &L->u.lk;
-    const uint8_t *res = S->hmem + Y->o_hres;
-    const int32_t *he = (const int32_t *)(res + Y->r_err);
-    const uint32_t *hn = (const uint32_t *)(res + Y->r_nr);
-    const uint32_t *hd = (const uint32_t *)(res + Y->r_depth);
-    const uint8_t *recs = res + Y->res_hdr;
-    size_t j = 0;
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        K->status[b] = 0;                       /* delivered; the decoder's code is in the requests' err */
-        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
-            const size_t r = K->req_ids[k];
-            K->err[r] = he[j];
-            K->nr[r] = hn[j];
-            K->depth[r] = hd[j];
-            memcpy(K->out + POM_LK_REC_SIZE * r, recs + POM_LK_REC_SIZE * j, POM_LK_REC_SIZE);
-        }
-    }
-    return 0;
-}
-
-/* (a lookup's requests: set by the caller, so nothing to mark unreached) */
-static const struct chunk_ops lk_ops = {"lookup", 0, lk_cap, lk_extra_cost, NULL, lk_layout,
-                                        lk_stage, lk_kernels, lk_collect, lk_unpack};
-
-int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                       struct pom_lookup_sink *sink)
-{
-    struct hbatch B = {.ops = &lk_ops, .src = src, .src_len = src_len, .status = sink->status,
-                       .is_lzo = sink->is_lzo, .sink = sink};
-    return pom_host_batch(&B, nblocks);
-}
-
-/* ------------------------------------------------------------------------ */
-/* Key/value gets: decode, chain walk and copy (itb_kvget.hip), values back   */
-/* ------------------------------------------------------------------------ */
-/* The lookups' partition, request order and staging, with the string keys in
- * the names' place: a string request whose key the caller's blob does not
- * hold gets no key bytes and a skey_off past the chunk's blob (the kernel's
- * rule 4 refuses it); one with sklen above 320 gets no key bytes either and
- * matches nothing.  The records are variable-length, so they come back as the
- * walks' do: the fixed-size results and the chunk's record total in one copy
- * queued behind the kernels, exactly that many record bytes in a second one
- * sized once the first is back.  Staging (host and device alike up to the
- * inputs' end; pom_layout_kvget):
- *   [src_off u64][dst_off u64][scan_off u64][requests, nreq][src_len u32][dst_cap u32]
- *   [status i32][out_len u32][adepth u8]
- *   [src bytes, 16-B aligned per block][keys]
- *   device: [decoded payloads][decoder scratch][first u64, nreq]
- *   both:   [total u64][err i32][nr u32][depth u32][len u32][lease u64], nreq each  <- D2H, one copy
- *           [the chunk's records, packed, unless lengths only]                    <- D2H, sized after the first
- * No other decoded byte leaves the device. */
-struct pom_kvget_buf {
-    struct pom_kvget_buf *next;
-    uint64_t pad;
-    uint8_t bytes[];
-};
-
-static int kg_key_ok(const struct pom_kvget_sink *K, const struct pom_kvget_req *q)
-{
-    return (q->kvflag & POM_KV_STR) && q->sklen <= POM_KV_VALUE_MAX && (size_t)q->skey_off + q->sklen <= K->keys_len;
-}
-
-static size_t kg_key_bytes(const struct pom_kvget_sink *K, const struct pom_kvget_req *q)
-{
-    return kg_key_ok(K, q) ? q->sklen : 0;
-}
-
-static size_t kg_cap(const struct hbatch *B, size_t b)
-{
-    const struct pom_kvget_sink *K = B->sink;
-    return K->cap[b];
-}
-
-static size_t kg_keys(const struct pom_kvget_sink *K, size_t b)
-{
-    size_t n = 0;
-    for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++)
-        n += kg_key_bytes(K, &K->req[K->req_ids[k]]);
-    return n;
-}
-
-/* the chunk budget counts the requests, their keys, their results and their records' room */
-static size_t kg_extra_cost(const struct hbatch *B, size_t b)
-{
-    const struct pom_kvget_sink *K = B->sink;
-    return (K->req_first[b + 1] - K->req_first[b]) *
-               (sizeof(struct pom_kvget_req) + 4 * sizeof(uint32_t) + 2 * sizeof(uint64_t) +
-                (K->lengths_only ? 0 : POM_KG_REC_MAX)) + kg_keys(K, b);
-}
-
-static void kg_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
-{
-    const struct pom_kvget_sink *K = B->sink;
-    size_t nreq = 0, keys = 0;
-    for (size_t i = 0; i < nb; i++) {
-        nreq += K->req_first[ids[i] + 1] - K->req_first[ids[i]];
-        keys += kg_keys(K, ids[i]);
-    }
-    pom_layout_kvget(L, ids, nb, nlzo, B->src_len, B->cap, nreq, keys, !K->lengths_only,
-                     lzo_mi355x_decompress_scratch((uint32_t)nlzo));
-}
-
-static int kg_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
-{
-    const struct pom_kvget_sink *K = B->sink;
-    const struct kvget_layout *Y = &L->u.kg;
-    if (Y->nreq > 0xFFFFFFFFu / POM_KG_REC_MAX || Y->keys_bytes > 0xFFFFFFF0u)
-        return -1;
-    struct pom_kvget_req *rq = (struct pom_kvget_req *)(h + Y->o_req);
-    uint8_t *ky = h + Y->o_keys;
-    size_t j = 0, at = 0;
-    pom_stage_inputs(L, h, B);
-    stage_scan(L, &Y->scan, h, K->adepth);
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
-            const struct pom_kvget_req *q = &K->req[K->req_ids[k]];
-            const size_t n = kg_key_bytes(K, q);
-            rq[j] = *q;
-            rq[j].itb = (uint32_t)i;            /* the chunk's own ITB index */
-            if (kg_key_ok(K, q)) {
-                rq[j].skey_off = (uint32_t)at;
-                if (n)
-                    memcpy(ky + at, K->keys + q->skey_off, n);
-                at += n;
-            } else {
-                rq[j].skey_off = 0xFFFFFFFFu;   /* outside the chunk's blob (read by string gets of sklen <= 320 only) */
-            }
-        }
-    }
-    return 0;
+                                    d + Y->o_blob, (uint32_t)Y->blob_bytes, (int32_t *)(res + Y->r_word[RW_ERR]),
+                                    (uint32_t *)(res + Y->r_word[RW_NR]), (uint32_t *)(res + Y->r_word[RW_DEPTH]),
+                                    res + Y->res_hdr, S->stream);
 }
 
 static int kg_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
 {
-    const struct kvget_layout *Y = &L->u.kg;
+    const struct req_layout *Y = &L->u.req;
     uint8_t *d = S->dmem, *res = d + Y->o_res;
     size_t queued;
     (void)B;
@@ -744,23 +568,26 @@ static int kg_kernels(struct slot *S, const struct layout *L, const struct hbatc
         return -1;
     if (lzo_mi355x_launch_kvget(d, (const uint64_t *)(d + Y->scan.o_scanoff), (const uint32_t *)(d + L->o_outlen),
                                 (const int32_t *)(d + L->o_status), d + Y->scan.o_adepth, (uint32_t)L->nb,
-                                (const struct pom_kvget_req *)(d + Y->o_req), (uint32_t)Y->nreq, d + Y->o_keys,
-                                (uint32_t)Y->keys_bytes, (int32_t *)(res + Y->r_err), (uint32_t *)(res + Y->r_nr),
-                                (uint32_t *)(res + Y->r_depth), (uint32_t *)(res + Y->r_len),
-                                (uint64_t *)(res + Y->r_lease), (uint64_t *)(d + Y->o_first), d + Y->o_pack, Y->rcap,
-                                S->stream) != 0)
+                                (const struct pom_kvget_req *)(d + Y->o_req), (uint32_t)Y->nreq, d + Y->o_blob,
+                                (uint32_t)Y->blob_bytes, (int32_t *)(res + Y->r_word[RW_ERR]),
+                                (uint32_t *)(res + Y->r_word[RW_NR]), (uint32_t *)(res + Y->r_word[RW_DEPTH]),
+                                (uint32_t *)(res + Y->r_word[RW_LEN]), (uint64_t *)(res + Y->r_lease),
+                                (uint64_t *)(d + Y->o_first), d + Y->o_pack, Y->rcap, S->stream) != 0)
         return -1;
     return results_back(S, Y->o_hres, Y->o_res, Y->res_bytes, &queued);
 }
 
-/* Once the lengths are back: the D2H of exactly the chunk's records. */
-static int kg_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
+/* Fixed records: the one copy.  Variable ones, once the lengths are back: the
+ * D2H of exactly the chunk's records. */
+static int req_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
 {
-    const struct pom_kvget_sink *K = B->sink;
-    const struct kvget_layout *Y = &L->u.kg;
+    const struct req_call *C = B->sink;
+    const struct req_layout *Y = &L->u.req;
     uint64_t total;
+    if (!C->K->spec->rec_max)
+        return results_back(S, Y->o_hres, Y->o_res, Y->res_bytes, packed);
     memcpy(&total, S->hmem + Y->o_hres, 8);
-    if (K->lengths_only)
+    if (!C->K->records)
         total = 0;
     if (total > Y->rcap)
         return -1;
@@ -772,61 +599,47 @@ static int kg_collect(struct slot *S, const struct layout *L, const struct hbatc
 }
 
 /* The fixed-size results go to their places in the caller's request order;
- * the records stay in a buffer of the sink until the caller knows the call's
- * own first[]. */
-static int kg_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
+ * variable records stay in a buffer of the sink until the caller knows the
+ * call's own first[]. */
+static int req_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
 {
-    struct pom_kvget_sink *K = B->sink;
-    const struct kvget_layout *Y = &L->u.kg;
-    const uint8_t *res = S->hmem + Y->o_hres;
-    const int32_t *he = (const int32_t *)(res + Y->r_err);
-    const uint32_t *hn = (const uint32_t *)(res + Y->r_nr);
-    const uint32_t *hd = (const uint32_t *)(res + Y->r_depth);
-    const uint32_t *hl = (const uint32_t *)(res + Y->r_len);
-    const uint64_t *hs = (const uint64_t *)(res + Y->r_lease);
-    struct pom_kvget_buf *buf = malloc(sizeof(*buf) + L->packed);
-    if (!buf)
-        return -1;
-    memcpy(buf->bytes, S->hmem + Y->o_hrec, L->packed);
-    size_t j = 0, at = 0;
-    for (size_t i = 0; i < L->nb; i++) {
-        const size_t b = L->ids[i];
-        K->status[b] = 0;                       /* delivered; the decoder's code is in the requests' err */
-        for (size_t k = K->req_first[b]; k < K->req_first[b + 1]; k++, j++) {
-            const size_t r = K->req_ids[k];
-            K->err[r] = he[j];
-            K->nr[r] = hn[j];
-            K->depth[r] = hd[j];
-            K->len[r] = hl[j];
-            K->lease[r] = hs[j];
-            K->recs[r] = !K->lengths_only && hl[j] && at + hl[j] <= L->packed ? buf->bytes + at : NULL;
-            at += hl[j];
-        }
+    struct req_call *C = B->sink;
+    struct pom_walk_buf *buf = NULL;
+    if (C->K->spec->rec_max) {
+        buf = malloc(sizeof(*buf) + L->packed);
+        if (!buf)
+            return -1;
+        memcpy(buf->bytes, S->hmem + L->u.req.o_hrec, L->packed);
     }
-    pthread_mutex_lock(&K->mu);
-    buf->next = K->bufs;
-    K->bufs = buf;
-    pthread_mutex_unlock(&K->mu);
+    pom_req_scatter(L, S->hmem, C->K, buf ? buf->bytes : NULL, L->packed);
+    if (buf)
+        keep_records(&C->K->bufs, &C->mu, buf);
     return 0;
 }
 
-void pom_kvget_sink_free(struct pom_kvget_sink *sink)
+/* (a request's results: set by the caller, so nothing to mark unreached) */
+static const struct chunk_ops lk_ops = {"lookup", 0, req_cap, req_extra_cost, NULL, req_layout,
+                                        req_stage, lk_kernels, req_collect, req_unpack};
+static const struct chunk_ops kg_ops = {"kvget", 0, req_cap, req_extra_cost, NULL, req_layout,
+                                        req_stage, kg_kernels, req_collect, req_unpack};
+
+static int req_batch(const struct chunk_ops *ops, const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                     struct pom_req_sink *sink)
 {
-    while (sink->bufs) {
-        struct pom_kvget_buf *next = sink->bufs->next;
-        free(sink->bufs);
-        sink->bufs = next;
-    }
+    struct req_call C = {sink, PTHREAD_MUTEX_INITIALIZER};
+    struct hbatch B = {.ops = ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
+                       .sink = &C};
+    const int rc = pom_host_batch(&B, nblocks);
+    pthread_mutex_destroy(&C.mu);
+    return rc;
 }
 
-/* (a get's requests: set by the caller, so nothing to mark unreached) */
-static const struct chunk_ops kg_ops = {"kvget", 0, kg_cap, kg_extra_cost, NULL, kg_layout,
-                                        kg_stage, kg_kernels, kg_collect, kg_unpack};
-
-int pom_kvget_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                      struct pom_kvget_sink *sink)
+int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks, struct pom_req_sink *sink)
 {
-    struct hbatch B = {.ops = &kg_ops, .src = src, .src_len = src_len, .status = sink->status,
-                       .is_lzo = sink->is_lzo, .sink = sink};
-    return pom_host_batch(&B, nblocks);
+    return req_batch(&lk_ops, src, src_len, nblocks, sink);
+}
+
+int pom_kvget_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks, struct pom_req_sink *sink)
+{
+    return req_batch(&kg_ops, src, src_len, nblocks, sink);
 }

@@ -170,9 +170,9 @@ int lzo_mi355x_launch_gc_scan(const uint8_t *payload, const uint64_t *payload_of
  * payload walked as staged.  Per block the decoder's status and out_len (0 and
  * src_len[b] when not is_lzo), and live, count and err as the walk's _dev call
  * gives them; recs[b] = the block's records, inside one of the per-chunk
- * buffers linked at bufs (the caller frees them with pom_walk_sink_free).
+ * buffers linked at bufs (the caller frees them with pom_walk_bufs_free).
  * Only the counts and the records are copied back. */
-struct pom_walk_buf;
+struct pom_walk_buf;                /* host_requests.h */
 struct pom_walk_sink {
     const uint8_t *is_lzo;
     const size_t *cap;
@@ -198,20 +198,6 @@ int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t
                         struct pom_walk_sink *sink);
 int pom_kvlist_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                        struct pom_walk_sink *sink);
-void pom_walk_sink_free(struct pom_walk_sink *sink);
-
-/* Host side (gc_scan.c), not part of the ABI: the header checks the walks'
- * host batches share (include/pom_gc.h pom_gc_scan_batch).  0 and the block a
- * record stands for -- its stored payload, whether that is an LZO1X stream,
- * the decode capacity h.zlen - 264 (0 when stored uncompressed), adepth and
- * h.entries -- or -EINVAL. */
-struct pom_walk_block {
-    const uint8_t *src;
-    size_t src_len, cap;
-    uint8_t is_lzo, adepth;
-    int32_t entries;
-};
-int pom_itb_walk_header(const uint8_t *rec, size_t rec_len, struct pom_walk_block *w);
 
 /* Host side (gc_scan.c), not part of the ABI: the two halves the walks' host
  * batches share around their pom_*_chunked call.  pom_walk_out names the
@@ -308,31 +294,6 @@ int lzo_mi355x_launch_lookup(const uint8_t *payload, const uint64_t *payload_off
                              uint32_t nreq, const uint8_t *names, uint32_t names_len, int32_t *err,
                              uint32_t *nr, uint32_t *depth, uint8_t *out, hipStream_t stream);
 
-/* Host side (host_records.c), not part of the ABI: pom_gc_scan_chunked's pipeline
- * (LZO records decoded, stored ones walked as staged) with the lookup behind
- * each chunk's decode and pom_col_read_chunked's request grouping (lookup.c).
- * Block b's requests are req[req_ids[k]] for k in [req_first[b], req_first[b +
- * 1]); an ITB and all its requests travel in one chunk, renumbered to the
- * chunk's own ITB indices, with their names (from names[0, names_len)) staged
- * behind them.  Per request err, nr, depth and the 136-byte record at out +
- * 136 * r, all in the caller's request order; a decoder's code reaches the
- * requests through err.  Only those come back. */
-struct pom_lookup_sink {
-    const uint8_t *is_lzo;
-    const size_t *cap;
-    const uint8_t *adepth;
-    const size_t *req_first, *req_ids;
-    const struct pom_lookup_req *req;
-    const uint8_t *names;
-    size_t names_len;
-    uint8_t *out;
-    int *err;
-    uint32_t *nr, *depth;
-    int32_t *status;
-};
-int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                       struct pom_lookup_sink *sink);
-
 /* The key/value point get's ITB walk (itb_kvget.hip): pom_kvget_dev of
  * include/pom_kvget.h, three launches on `stream`. */
 struct pom_kvget_req;
@@ -343,34 +304,22 @@ int lzo_mi355x_launch_kvget(const uint8_t *payload, const uint64_t *payload_off,
                             uint32_t *nr, uint32_t *depth, uint32_t *len, uint64_t *lease,
                             uint64_t *first, uint8_t *out, uint64_t out_cap, hipStream_t stream);
 
-/* Host side (host_records.c), not part of the ABI: pom_lookup_chunked's
- * partition, request grouping and key staging (kvget.c) with the get behind
- * each chunk's decode.  Per request err, nr, depth, len and lease in the
- * caller's request order.  The records are variable-length: each chunk's come
- * back packed, in the chunk's own request order, into a buffer linked at bufs,
- * and recs[r] points at request r's (NULL when lengths_only, or len[r] == 0);
- * the caller places them and frees the buffers with pom_kvget_sink_free. */
-struct pom_kvget_buf;
-struct pom_kvget_sink {
-    const uint8_t *is_lzo;
-    const size_t *cap;
-    const uint8_t *adepth;
-    const size_t *req_first, *req_ids;
-    const struct pom_kvget_req *req;
-    const uint8_t *keys;
-    size_t keys_len;
-    int lengths_only;               /* no emit launch, no record comes back */
-    int *err;
-    uint32_t *nr, *depth, *len;
-    uint64_t *lease;
-    const uint8_t **recs;
-    int32_t *status;
-    struct pom_kvget_buf *bufs;
-    pthread_mutex_t mu;             /* bufs: chunks of a multi-GPU batch finish on several threads */
-};
+/* Host side (host_records.c), not part of the ABI: the request operations.
+ * pom_gc_scan_chunked's pipeline (LZO records decoded, stored ones walked as
+ * staged) with the lookup or the get behind each chunk's decode and
+ * pom_col_read_chunked's request grouping.  An ITB and all its requests travel
+ * in one chunk, renumbered to the chunk's own ITB indices, with their names or
+ * keys staged behind them; a decoder's code reaches the requests through err.
+ * The sink (struct pom_req_sink, host_requests.h) is one for both kinds, set
+ * up by pom_req_begin: a lookup's caller adds `fixed`, where the 136-byte
+ * records go in request order; a get's caller adds `records` and places the
+ * records recs[] points at before pom_req_finish frees their buffers.  Only
+ * the kind's words and those records come back. */
+struct pom_req_sink;
+int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                       struct pom_req_sink *sink);
 int pom_kvget_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
-                      struct pom_kvget_sink *sink);
-void pom_kvget_sink_free(struct pom_kvget_sink *sink);
+                      struct pom_req_sink *sink);
 
 #ifdef __cplusplus
 }

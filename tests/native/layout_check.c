@@ -1,8 +1,8 @@
 /* layout_check.c -- the staging layouts of the host batches
  * (pomegranate_amd/csrc/host_layout.c) checked on the CPU, under
  * AddressSanitizer and UBSan: for every operation and every combination of
- * block count, LZO prefix, sizes, request counts, name lengths and kvlist
- * options below,
+ * block count, LZO prefix, sizes, request counts, blob lengths, both request
+ * kinds (the get with and without records) and kvlist options below,
  *   - every array starts at a multiple of its element size;
  *   - the input bytes start at a multiple of 256, each block's at a multiple of 16;
  *   - the regions of the host staging are pairwise disjoint and end within
@@ -19,9 +19,9 @@
 #include <string.h>
 
 #include "host_layout.h"
+#include "host_requests.h"
 #include "pom_column.h"
 #include "pom_kvlist.h"
-#include "pom_lookup.h"
 
 enum { HOST = 1, DEV = 2, BOTH = 3 };
 enum { PLAIN, UPLOAD, RESULT };         /* UPLOAD: inside the H2D span; RESULT: also inside the result D2H span */
@@ -193,6 +193,59 @@ static void walk_case(const char *name, const struct walk_spec *W, const size_t 
     check(&L, K->res_off, K->res_bytes);
 }
 
+/* A request operation's chunk: nreq requests of bloblen blob bytes each. */
+static void req_case(const char *name, const struct req_spec *Q, const size_t *ids, size_t nb, size_t nlzo,
+                     const size_t *src_len, const size_t *cap, size_t nreq, size_t bloblen, int records, size_t scratch)
+{
+    static const char *kReqWord[RW_N] = {"err", "nr", "depth", "len"};
+    struct layout L;
+    what = name;
+    nR = 0;
+    pom_layout_req(&L, ids, nb, nlzo, src_len, cap, Q, nreq, nreq * bloblen, records, scratch);
+    const struct req_layout *K = &L.u.req;
+    add_shared(&L, UPLOAD);
+    add("scan_off", K->scan.o_scanoff, 8, 8 * nb, BOTH, UPLOAD);
+    add("requests", K->o_req, 8, POM_REQ_SIZE * nreq, BOTH, UPLOAD);
+    add("adepth", K->scan.o_adepth, 1, nb, BOTH, UPLOAD);
+    add_bytes(&L, src_len, cap, scratch);
+    add("blob", K->o_blob, 1, nreq * bloblen, BOTH, UPLOAD);
+    if (K->nreq != nreq || K->blob_bytes != nreq * bloblen)
+        fail("request or blob count", NULL, NULL);
+    if (K->rcap != (Q->rec_max && records ? POM_ALIGN_UP(Q->rec_max * nreq, 16) : 0))
+        fail("record room", NULL, NULL);
+    struct region f[2 + RW_N];
+    size_t nf = 0, at = 0;
+    if (Q->rec_max) {
+        /* device first[nreq + 1]: its last entry is the chunk total, the first word that comes back */
+        add("first", K->o_first, 8, 8 * nreq, DEV, PLAIN);
+        if (K->o_first + 8 * nreq != K->o_res)
+            fail("first[nreq] is not the results' first word", NULL, NULL);
+        f[nf++] = (struct region){"total", 0, 8, 8, 0, 0};
+    }
+    for (size_t w = 0; w < Q->nwords; w++)
+        f[nf++] = (struct region){kReqWord[w], K->r_word[w], 4, 4 * nreq, 0, 0};
+    if (Q->lease)
+        f[nf++] = (struct region){"lease", K->r_lease, 8, 8 * nreq, 0, 0};
+    if (Q->rec_fixed) {
+        check_results(&L, K->o_res, K->o_hres, K->res_hdr, K->res_bytes, f, nf, Q->rec_fixed * nreq);
+        return;
+    }
+    /* variable records: the fields alone are the first copy, the packed records a second, 16-byte aligned */
+    for (size_t i = 0; i < nf; i++) {
+        if (f[i].off != at)
+            fail("result header field out of place", &f[i], NULL);
+        at += f[i].bytes;
+        add(f[i].name, K->o_res + f[i].off, f[i].elem, f[i].bytes, DEV, PLAIN);
+        add(f[i].name, K->o_hres + f[i].off, f[i].elem, f[i].bytes, HOST, PLAIN);
+    }
+    if (K->res_bytes != at)
+        fail("result span is not its fields", NULL, NULL);
+    /* (the device's lie behind first[] and the results, 8-byte aligned: the emit kernel takes any alignment) */
+    add("records", K->o_pack, 8, K->rcap, DEV, PLAIN);
+    add("host records", K->o_hrec, 16, K->rcap, HOST, PLAIN);
+    check(&L, 0, 0);
+}
+
 /* A group of k single calls: call i has the a + i-th size as input, the c + 2i-th as room. */
 static const size_t kScSizes[] = {0, 1, 255, 256, 257, (3u << 20) + 5, 5u << 20};
 
@@ -308,23 +361,11 @@ int main(void)
                     walk_case("kvlist", &kv, ids, nb, nlzo, src_len, cap, scratch);
                 }
             for (size_t q = 0; q < 3; q++)
-                for (size_t namelen = 0; namelen <= 255; namelen += 255) {
-                    const size_t nreq = nb * kReqs[q], names = nreq * namelen;
-                    what = "lookup";
-                    nR = 0;
-                    pom_layout_lookup(&L, ids, nb, nlzo, src_len, cap, nreq, names, scratch);
-                    const struct lookup_layout *K = &L.u.lk;
-                    add_shared(&L, UPLOAD);
-                    add("scan_off", K->scan.o_scanoff, 8, 8 * nb, BOTH, UPLOAD);
-                    add("requests", K->o_req, 8, sizeof(struct pom_lookup_req) * nreq, BOTH, UPLOAD);
-                    add("adepth", K->scan.o_adepth, 1, nb, BOTH, UPLOAD);
-                    add_bytes(&L, src_len, cap, scratch);
-                    add("names", K->o_names, 1, names, BOTH, UPLOAD);
-                    if (K->nreq != nreq || K->names_bytes != names)
-                        fail("request or name count", NULL, NULL);
-                    const struct region lf[] = {{"err", K->r_err, 4, 4 * nreq, 0, 0}, {"nr", K->r_nr, 4, 4 * nreq, 0, 0},
-                                                {"depth", K->r_depth, 4, 4 * nreq, 0, 0}};
-                    check_results(&L, K->o_res, K->o_hres, K->res_hdr, K->res_bytes, lf, 3, POM_LK_REC_SIZE * nreq);
+                for (size_t bloblen = 0; bloblen <= 255; bloblen += 255) {
+                    req_case("lookup", &pom_req_lookup, ids, nb, nlzo, src_len, cap, nb * kReqs[q], bloblen, 0, scratch);
+                    for (int records = 0; records < 2; records++)
+                        req_case("kvget", &pom_req_kvget, ids, nb, nlzo, src_len, cap, nb * kReqs[q], bloblen, records,
+                                 scratch);
                 }
         }
     }

@@ -298,8 +298,10 @@ def test_batch_itbid_check_and_just_split(oracle, families):
 @pytest.fixture(scope="module")
 def chunky(oracle):
     """60 records of about 50 KB, every fourth stored uncompressed, with
-    shuffled requests to all of them: several chunks under chunk_mb=1.
-    (stored, req, names, want)."""
+    shuffled requests to all of them: several chunks under chunk_mb=1.  ITB 37
+    also has a name the staging refuses (namelen 256: -EINVAL) and one of
+    length 0, so that a chunk whose name offsets are not the caller's carries
+    both.  (stored, req, names, want)."""
     recs, items = [], []
     for b in range(60):
         n_ites = 60 + 7 * (b % 9)
@@ -307,6 +309,10 @@ def chunky(oracle):
         recs.append(rec)
         items += U.hits_for(rec, b, range(b % 4, n_ites, 4)) + U.misses_for(rec, b, b % n_ites)
     req, names = lookup.requests(items)
+    odd = req[req["itb"] == 37][:2].copy()
+    odd["flag"] = U.BY_NAME
+    odd["namelen"] = [256, 0]
+    req = np.concatenate([req, odd])
     req = np.ascontiguousarray(req[np.random.default_rng(11).permutation(len(req))])
     want = U.expect([U.payload_of(r) for r in recs], [8] * 60, req, names)
     return [r if b % 4 == 1 else U.lzo_record(oracle, r) for b, r in enumerate(recs)], req, names, want
