@@ -1,21 +1,31 @@
 /*
- * pom_gc.h -- the MDSL garbage collector's data scan on the MI355X
- * (liblzo_mi355x.so): decode ITBs and return the live column ranges, so that
- * no decoded payload byte has to leave the GPU.
+ * pom_gc.h -- the MDSL garbage collector's data pass on the MI355X
+ * (liblzo_mi355x.so): decode ITBs, walk their live column ranges, merge them
+ * as the collector's range tree does, and return the merged map with its sums,
+ * so that neither a decoded payload byte nor a per-file range has to leave the
+ * GPU.
  *
  * Per ITB, mdsl_gc_data_round (mdsl/gc.c:815-1013) reads the record, decodes
  * it (itb_lzo_decompress, mdsl/gc.c:945-955) and walks the ITE bitmap
  * (mdsl/gc.c:968-993), handing each live ITE to __add_to_brtree
- * (mdsl/gc.c:788-802), which keeps [offset, offset + len + 1) of one column
- * when len > 0.  These entry points batch the decode and the walk:
+ * (mdsl/gc.c:788-802), which adds [offset, offset + len + 1) of one column to
+ * a merging range tree when len > 0 (brt_add, lib/brtree.c:44-108).
+ * mdsl_gc_data_stat (mdsl/gc.c:1020-1113) then walks the tree in order
+ * (brt_loop_on_ranges) and folds it into gds->valid and gds->max
+ * (gc_data_stat_cb, mdsl/gc.c:746-753).  These entry points batch all of it:
  *
  *   pom_gc_scan_dev    <- the bitmap walk and __add_to_brtree's range
  *                         mdsl/gc.c:968-993, :788-802 (payloads in HBM)
  *   pom_gc_scan_batch  <- the decode switch and the walk of one round
  *                         mdsl/gc.c:945-993 (records in host memory)
+ *   pom_gc_merge_dev   <- brt_add, brt_loop_on_ranges and gc_data_stat_cb
+ *                         over ranges in HBM
+ *   pom_gc_stat_batch  <- all of the above for records in host memory, with
+ *                         the extents of earlier rounds
  *
- * The file walk, hole detection, the range lookup and the tree itself stay
- * with the caller (compose pom_itb_read_batch with pom_gc_scan_batch).
+ * The file walk, hole detection (__is_hole), the range lookup, and gds->total
+ * with gds->hole = total - valid, which need the data file, stay with the
+ * caller (compose pom_itb_read_batch with pom_gc_stat_batch).
  */
 #ifndef POM_GC_H
 #define POM_GC_H 1
@@ -107,6 +117,65 @@ int pom_gc_scan_dev(const uint8_t *payload, const uint64_t *payload_off,
  * LZO_E_OUT_OF_MEMORY, or LZO_E_ERROR when the GPU path is unusable. */
 int pom_gc_scan_batch(const uint8_t *const *rec, const size_t *rec_len, size_t n, int column,
                       struct pom_gc_range *ranges, size_t ranges_cap, size_t *first,
+                      uint32_t *live, int *err, int *len_ok, int *entries_ok);
+
+/* What the tree computes, whatever the order of insertion: sort the ranges by
+ * low; a range starts a new extent if and only if its low is strictly greater
+ * than the largest high seen so far (touching ranges merge: the tree's compare
+ * returns 0 for them); an extent is [first low, largest high); the walk
+ * delivers the extents in ascending order.  A range with high <= low (a wrap
+ * of offset + len + 1; the tree's comparator is inconsistent on such a node)
+ * is not merged, only counted.
+ *   valid     the sum of high - low over the extents (gds->valid), mod 2^64
+ *   max       the last extent's high (gds->max), 0 with none
+ *   nout      the extents
+ *   nin       the ranges that came in
+ *   nwrapped  those of them with high <= low */
+struct pom_gc_stat {
+    uint64_t valid, max, nout, nin, nwrapped;
+};
+
+/* The most ranges one pom_gc_merge_dev call takes. */
+#define POM_GC_MERGE_MAX (1u << 30)
+
+/* Bytes of device scratch pom_gc_merge_dev needs for n ranges (0 for n above
+ * POM_GC_MERGE_MAX). */
+size_t pom_gc_merge_scratch(uint32_t n);
+
+/* brt_add, brt_loop_on_ranges and gc_data_stat_cb over n ranges in device
+ * memory: a radix sort by low, a running maximum of high, the extents' heads,
+ * the merged map; enqueue only, and the number of launches follows from n.
+ * in is not modified and may sit at any 8-byte alignment, as may out, stat and
+ * scratch; in may be the ranges of a pom_gc_scan_dev queued before on the same
+ * stream.  Extent k goes to out[k] for k < out_cap, ascending; stat is always
+ * written in full (with n == 0 in is not touched).  Nothing is written outside
+ * stat, scratch[0, scratch_bytes) and out[0, min(nout, out_cap)).  Every
+ * pointer is device memory.  Returns 0, or -1 when a launch failed, scratch
+ * has fewer than pom_gc_merge_scratch(n) bytes or is not 8-byte aligned, or n
+ * is above POM_GC_MERGE_MAX. */
+int pom_gc_merge_dev(const struct pom_gc_range *in, uint32_t n,
+                     void *scratch, size_t scratch_bytes,
+                     struct pom_gc_range *out, uint64_t out_cap,
+                     struct pom_gc_stat *stat, void *stream);
+
+/* mdsl_gc_data_stat's tree for n ITB records in host memory and one column:
+ * per ITB exactly pom_gc_scan_batch's live, err, len_ok and entries_ok; the
+ * ranges of every ITB with err[b] == 0 are merged on the GPU, chunk by chunk,
+ * and only each chunk's merged map comes back.  The chunks' maps and seed --
+ * nseed extents of earlier rounds (mdsl_gc_data_stat runs redo_round into one
+ * tree), ascending and disjoint with gaps of at least 1, may be NULL when
+ * nseed is 0 -- are folded on the host with the same rule, so the result does
+ * not depend on how the batch was cut.  merged gets the first merged_cap
+ * extents; stat describes the whole folded map, with nin and nwrapped the
+ * ITBs' ranges (the seed's are not counted): gds->valid = stat->valid,
+ * gds->max = stat->max.  Returns 0; POM_GC_E_NOSPACE when stat->nout exceeds
+ * merged_cap (everything else complete, only merged[0, merged_cap) written);
+ * -EINVAL (column outside 0 ... 5, a seed that is not ascending and disjoint);
+ * LZO_E_OUT_OF_MEMORY; LZO_E_ERROR when the GPU path is unusable (nothing is
+ * computed then). */
+int pom_gc_stat_batch(const uint8_t *const *rec, const size_t *rec_len, size_t n, int column,
+                      const struct pom_gc_range *seed, size_t nseed,
+                      struct pom_gc_range *merged, size_t merged_cap, struct pom_gc_stat *stat,
                       uint32_t *live, int *err, int *len_ok, int *entries_ok);
 
 #ifdef __cplusplus

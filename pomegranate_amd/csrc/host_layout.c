@@ -14,6 +14,14 @@ size_t pom_walk_max_ites(size_t n)
     return ites < 1024 ? ites : 1024;
 }
 
+size_t pom_gc_max_ranges(size_t n, unsigned adepth)
+{
+    const size_t ites = pom_walk_max_ites(n);
+    if (adepth < 1 || adepth > 10)
+        return 0;
+    return ites < ((size_t)1 << adepth) ? ites : (size_t)1 << adepth;
+}
+
 /* The next `bytes` of the staging: their offset. */
 static size_t take(size_t *o, size_t bytes)
 {
@@ -123,6 +131,48 @@ void pom_layout_walk(struct layout *L, const size_t *ids, size_t nb, size_t nlzo
     L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
     K->o_mask = take(&o, masks);
     K->o_pack = take(&o, r);
+    L->dtotal = o;
+}
+
+void pom_layout_gcstat(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                       const size_t *cap, const struct walk_spec *W, size_t scratch, size_t nmerge,
+                       size_t merge_scratch)
+{
+    size_t in, out, o = 0;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct gcstat_layout *G = &L->u.gcstat;
+    struct walk_layout *K = &G->walk;
+    const size_t r = nmerge * 16;
+    G->nmerge = nmerge;
+    K->rcap = r;
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    K->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_first = take(&o, 8 * (nb + 1));
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    K->res_off = o;
+    for (size_t w = 0; w < W->nwords; w++)
+        K->o_word[W->words[w]] = take(&o, 4 * nb);
+    o = POM_ALIGN_UP(o, 8);
+    G->o_stat = take(&o, 5 * 8);
+    K->res_bytes = o - K->res_off;
+    L->o_status = K->o_word[WW_STATUS];
+    L->o_outlen = K->o_word[WW_OUTLEN];
+    K->scan.o_adepth = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    L->o_dst = o;
+    K->o_hmask = o;
+    K->o_hrec = o;
+    L->htotal = o + r;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_mask = o;
+    K->o_pack = take(&o, POM_ALIGN_UP(r, 256));
+    G->mscr_bytes = merge_scratch;
+    G->o_mscr = take(&o, POM_ALIGN_UP(merge_scratch, 256));
+    G->o_merged = take(&o, r);
     L->dtotal = o;
 }
 

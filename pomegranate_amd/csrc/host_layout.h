@@ -65,6 +65,21 @@ struct walk_layout {
     size_t o_hmask, o_hrec;     /* host only: masks, records */
 };
 
+/* The GC data stat: the GC scan's walk with the merge of its ranges behind it
+ * (gc_merge.hip).  The walk's layout comes first, so that what serves the walks
+ * serves this chunk too; its records' room is the merge's input, nmerge ranges
+ * (zeroed before the scan, so that the places the scan leaves are dropped
+ * ranges).  The chunk's struct pom_gc_stat lies behind the result words, 8-byte
+ * aligned, inside their D2H span; the merged map comes back in a second copy
+ * sized by its nout. */
+struct gcstat_layout {
+    struct walk_layout walk;    /* o_pack: the ranges; o_hrec: the host's merged map; rcap: 16 * nmerge */
+    size_t nmerge;              /* ranges the chunk's ITBs can emit at the most */
+    size_t o_stat;              /* struct pom_gc_stat, host and device alike */
+    size_t o_mscr, mscr_bytes;  /* device only: the merge's scratch */
+    size_t o_merged;            /* device only: the merged map, room for nmerge extents */
+};
+
 /* Column reads.  The results -- a header of four arrays, then the slices --
  * lie alike on both sides (device o_res, host o_hres) and come back in one
  * copy; the r_ offsets are relative to the results' start. */
@@ -135,6 +150,7 @@ struct layout {
     union {
         struct codec_layout codec;
         struct walk_layout walk;
+        struct gcstat_layout gcstat;    /* (starts with the walk's) */
         struct col_layout col;
         struct req_layout req;
     } u;
@@ -147,6 +163,11 @@ void pom_layout_codec(struct layout *L, const size_t *ids, size_t nb, const size
                       const size_t *cap, size_t scratch);
 void pom_layout_walk(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
                      const size_t *cap, const struct walk_spec *W, size_t scratch);
+/* The GC scan's walk layout (W: its spec) with the merge behind it: nmerge
+ * ranges at the most, merge_scratch bytes of scratch for them. */
+void pom_layout_gcstat(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                       const size_t *cap, const struct walk_spec *W, size_t scratch, size_t nmerge,
+                       size_t merge_scratch);
 /* slice_bytes: the requests' clamped lengths, each rounded up to 16 */
 void pom_layout_col(struct layout *L, const size_t *ids, size_t nb, const size_t *src_len,
                     const size_t *cap, size_t nreq, size_t slice_bytes, size_t scratch);
@@ -179,6 +200,10 @@ void pom_layout_single(struct single_layout *L, size_t k, const size_t *src_len,
 
 /* The ITEs a payload of n bytes can hold: what a walk can emit at the most. */
 size_t pom_walk_max_ites(size_t n);
+/* The ranges the GC scan can emit for an ITB of that payload size and adepth:
+ * one per ITE it holds and per bitmap bit below 1 << adepth (none for an
+ * adepth outside 1 ... 10). */
+size_t pom_gc_max_ranges(size_t n, unsigned adepth);
 
 #ifdef __cplusplus
 }

@@ -4,11 +4,13 @@
  * lzo_host.c (host_pipeline.h).  The three walks -- the GC scan
  * (itb_scan.hip), the directory listing (itb_dents.hip), the key/value
  * listing (itb_keys.hip) -- share one layout, one staging and one delivery,
- * told apart by their list of result words and their record unit; the column
+ * told apart by their list of result words and their record unit; the GC data
+ * stat is the GC scan with the merge of the chunk's ranges behind it
+ * (gc_merge.hip) and the merged map in the records' place; the column
  * read (col_slice.hip), the lookup (itb_find.hip) and the key/value get
  * (itb_kvget.hip) carry requests, the last two as one operation told apart by
  * a descriptor (struct req_spec) and their kernels.  Their callers (gc_scan.c,
- * readdir.c, kvlist.c, column_codec.c, lookup.c, kvget.c) select the blocks
+ * gc_stat.c, readdir.c, kvlist.c, column_codec.c, lookup.c, kvget.c) select the blocks
  * and put the results in the caller's order.
  */
 #include <pthread.h>
@@ -20,6 +22,7 @@
 #include "lzo_mi355x.h"
 #include "minilzo.h"
 #include "pom_column.h"
+#include "pom_gc.h"
 #include "pom_kvget.h"
 #include "pom_kvlist.h"
 #include "pom_lookup.h"
@@ -88,7 +91,12 @@ static void keep_records(struct pom_walk_buf **bufs, pthread_mutex_t *mu, struct
  *   kvlist    [status i32][out_len u32][live u32][dnum u32][bytes u32][keybytes u32][err i32], 324 an ITE;
  *             the call's needle is staged once per chunk, the emit masks stay on the
  *             device unless the caller asked for them, a count-only call has no records
- * No other decoded byte leaves the device. */
+ * No other decoded byte leaves the device.
+ * The GC data stat is the GC scan with the merge of the chunk's ranges behind it
+ * (pom_layout_gcstat): its result words are followed by the chunk's struct
+ * pom_gc_stat in the same D2H, the device staging by the merge's scratch and the
+ * merged map, and the second D2H brings exactly stat.nout extents; no range
+ * leaves the device. */
 static const uint8_t gc_words[] = {WW_STATUS, WW_OUTLEN, WW_LIVE, WW_COUNT, WW_ERR};
 static const uint8_t rd_words[] = {WW_STATUS, WW_OUTLEN, WW_LIVE, WW_COUNT, WW_BYTES, WW_ERR};
 static const uint8_t kv_words[] = {WW_STATUS, WW_OUTLEN, WW_LIVE, WW_COUNT, WW_BYTES, WW_KEYBYTES, WW_ERR};
@@ -308,6 +316,138 @@ static int walk_batch(const struct chunk_ops *ops, const struct walk_spec *spec,
 int pom_gc_scan_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks, struct pom_walk_sink *sink)
 {
     return walk_batch(&gc_ops, &gc_spec, src, src_len, nblocks, sink);
+}
+
+/* The GC data stat.  The merge runs over all nmerge places of the ranges' room,
+ * which is zeroed before the scan: a place the scan leaves is {0, 0}, a dropped
+ * range, and the chunk's nwrapped is corrected for them once the counts are back
+ * (the number of ranges is known on the device only, the number of launches
+ * must follow from what the host knows). */
+struct gcstat_call {
+    struct walk_call C;             /* first: the walks' callbacks see their call */
+    struct pom_gc_stat_sink *M;
+};
+
+static size_t gs_max_ranges(const struct hbatch *B, size_t b)
+{
+    const struct walk_call *C = B->sink;
+    return pom_gc_max_ranges(C->G->is_lzo[b] ? C->G->cap[b] : B->src_len[b], C->G->adepth[b]);
+}
+
+/* the chunk budget counts a range's place, its extent's, and the sort's two buffers */
+static size_t gs_extra_cost(const struct hbatch *B, size_t b)
+{
+    return gs_max_ranges(B, b) * (2 * sizeof(struct pom_gc_range) + 32 + 8);
+}
+
+static void gs_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    const struct walk_call *C = B->sink;
+    size_t nm = 0;
+    for (size_t i = 0; i < nb; i++)
+        nm += gs_max_ranges(B, ids[i]);
+    /* (a chunk past the merge's bound gets no scratch, and its kernels refuse to run) */
+    pom_layout_gcstat(L, ids, nb, nlzo, B->src_len, B->cap, &C->spec, lzo_mi355x_decompress_scratch((uint32_t)nlzo),
+                      nm, nm <= POM_GC_MERGE_MAX ? pom_gc_merge_scratch((uint32_t)nm) : 0);
+}
+
+static int gs_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct walk_call *C = B->sink;
+    const struct gcstat_layout *G = &L->u.gcstat;
+    const struct walk_layout *K = &G->walk;
+    uint8_t *d = S->dmem;
+    struct pom_gc_range *ranges = (struct pom_gc_range *)(d + K->o_pack);
+    if (G->nmerge > POM_GC_MERGE_MAX)
+        return -1;
+    int rc = pom_decode_lzo_blocks(S, L, 0);
+    if (rc == 0 && K->rcap && hipMemsetAsync(ranges, 0, K->rcap, S->stream) != hipSuccess)
+        rc = -1;
+    if (rc == 0)
+        rc = lzo_mi355x_launch_gc_scan(d, (const uint64_t *)(d + K->scan.o_scanoff), dword(S, L, WW_OUTLEN),
+                                       (const int32_t *)dword(S, L, WW_STATUS), d + K->scan.o_adepth, (uint32_t)L->nb,
+                                       (uint32_t)C->G->column, dword(S, L, WW_LIVE), dword(S, L, WW_COUNT),
+                                       (uint64_t *)(d + K->o_first), ranges, G->nmerge,
+                                       (int32_t *)dword(S, L, WW_ERR), S->stream);
+    if (rc == 0)
+        rc = pom_gc_merge_dev(ranges, (uint32_t)G->nmerge, d + G->o_mscr, G->mscr_bytes,
+                              (struct pom_gc_range *)(d + G->o_merged), G->nmerge,
+                              (struct pom_gc_stat *)(d + G->o_stat), S->stream);
+    return walk_words_back(S, L, C, rc);
+}
+
+/* Once the counts and the chunk's stat are back: the D2H of exactly its extents. */
+static int gs_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
+{
+    const struct gcstat_layout *G = &L->u.gcstat;
+    const struct pom_gc_stat *st = (const struct pom_gc_stat *)(S->hmem + G->o_stat);
+    (void)B;
+    if (st->nout > G->nmerge)
+        return -1;
+    const size_t total = (size_t)st->nout * sizeof(struct pom_gc_range);
+    if (total && hipMemcpyAsync(S->hmem + G->walk.o_hrec, S->dmem + G->o_merged, total, hipMemcpyDeviceToHost,
+                                S->stream) != hipSuccess)
+        return -1;
+    *packed = total;
+    return 0;
+}
+
+static int gs_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct gcstat_call *Y = B->sink;
+    const struct walk_call *C = &Y->C;
+    const struct gcstat_layout *G = &L->u.gcstat;
+    struct pom_walk_sink *W = C->G;
+    const uint8_t *h = S->hmem;
+    const struct pom_gc_stat *st = (const struct pom_gc_stat *)(h + G->o_stat);
+    const uint32_t *n = (const uint32_t *)(h + G->walk.o_word[WW_COUNT]);
+    uint32_t *to[WW_N];
+    sink_words(C, to);
+    struct pom_walk_buf *buf = malloc(sizeof(*buf) + L->packed);
+    if (!buf)
+        return -1;
+    uint64_t nin = 0;
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i];
+        for (size_t w = 0; w < C->spec.nwords; w++)
+            to[w][b] = ((const uint32_t *)(h + G->walk.o_word[C->spec.words[w]]))[i];
+        W->recs[b] = NULL;
+        nin += n[i];
+    }
+    /* every place of the ranges' room the scan left was counted as a dropped range */
+    if (nin > G->nmerge || st->nin != G->nmerge || st->nwrapped < G->nmerge - nin) {
+        free(buf);
+        return -1;
+    }
+    memcpy(buf->bytes, h + G->walk.o_hrec, L->packed);
+    buf->pad = st->nout;
+    pthread_mutex_lock(&W->mu);
+    buf->next = Y->M->maps;
+    Y->M->maps = buf;
+    Y->M->nin += nin;
+    Y->M->nwrapped += st->nwrapped - (G->nmerge - nin);
+    pthread_mutex_unlock(&W->mu);
+    return 0;
+}
+
+static const struct chunk_ops gs_ops = {"gc stat", 0, walk_cap, gs_extra_cost, walk_unreached, gs_layout,
+                                        walk_stage, gs_kernels, gs_collect, gs_unpack};
+
+int pom_gc_stat_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                        struct pom_walk_sink *sink, struct pom_gc_stat_sink *maps)
+{
+    struct gcstat_call Y = {{sink, gc_spec}, maps};
+    uint32_t *to[WW_N];
+    sink_words(&Y.C, to);
+    for (size_t b = 0; b < nblocks; b++) {
+        for (size_t w = 0; w < gc_spec.nwords; w++)
+            if (gc_spec.words[w] != WW_STATUS && gc_spec.words[w] != WW_ERR)
+                to[w][b] = 0;
+        sink->recs[b] = NULL;
+    }
+    struct hbatch B = {.ops = &gs_ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
+                       .sink = &Y};
+    return pom_host_batch(&B, nblocks);
 }
 
 int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks, struct pom_walk_sink *sink)

@@ -199,6 +199,19 @@ int pom_readdir_chunked(const uint8_t *const *src, const size_t *src_len, size_t
 int pom_kvlist_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                        struct pom_walk_sink *sink);
 
+/* Host side (host_records.c), not part of the ABI: pom_gc_scan_chunked with the
+ * merge of each chunk's ranges queued behind its walk (gc_merge.hip; gc_stat.c).
+ * The per-block results are the scan's, but no range comes back (recs[b] stays
+ * NULL): each delivered chunk links its merged map at maps (pad: its extents;
+ * the caller frees them with pom_walk_bufs_free) and adds its ranges, and those
+ * of them with high <= low, to nin and nwrapped, all under the sink's mu. */
+struct pom_gc_stat_sink {
+    struct pom_walk_buf *maps;
+    uint64_t nin, nwrapped;
+};
+int pom_gc_stat_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                        struct pom_walk_sink *sink, struct pom_gc_stat_sink *maps);
+
 /* Host side (gc_scan.c), not part of the ABI: the two halves the walks' host
  * batches share around their pom_*_chunked call.  pom_walk_out names the
  * caller's outputs: out_cap and first[] count units of `unit` bytes (16-byte

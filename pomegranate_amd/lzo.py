@@ -62,7 +62,7 @@ EXPORTS = (
     "pom_xnet_frame", "pom_xnet_parse", "pom_xnet_itb_reply_batch", "pom_xnet_itb_wb_batch",
     "pom_xnet_itb_recv_batch",
     # include/pom_gc.h
-    "pom_gc_scan_dev", "pom_gc_scan_batch",
+    "pom_gc_scan_dev", "pom_gc_scan_batch", "pom_gc_merge_scratch", "pom_gc_merge_dev", "pom_gc_stat_batch",
     # include/pom_readdir.h
     "pom_readdir_dev", "pom_readdir_batch",
     # include/pom_lookup.h
