@@ -248,3 +248,38 @@ void pom_layout_req(struct layout *L, const size_t *ids, size_t nb, size_t nlzo,
     K->o_pack = take(&o, K->rcap);
     L->dtotal = o;
 }
+
+void pom_layout_check(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, int masks, size_t scratch)
+{
+    size_t in, out, o = 0, r = 0;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct itb_check_layout *K = &L->u.check;
+    K->masks = masks != 0;
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    K->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_hdr = take(&o, 32 * nb);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    L->o_status = take(&o, 4 * nb);
+    L->o_outlen = take(&o, 4 * nb);
+    K->scan.o_adepth = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    L->o_dst = o;
+    K->r_status = take(&r, 4 * nb);
+    K->r_outlen = take(&r, 4 * nb);
+    K->r_err = take(&r, 4 * nb);
+    r = POM_ALIGN_UP(r, 8);
+    K->r_report = take(&r, 48 * nb);
+    K->r_smask = take(&r, K->masks ? 256 * nb : 0);
+    K->r_imask = take(&r, K->masks ? 128 * nb : 0);
+    K->res_bytes = r;
+    K->o_hres = o;
+    L->htotal = o + K->res_bytes;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_res = take(&o, POM_ALIGN_UP(K->res_bytes, 256));
+    L->dtotal = o;
+}

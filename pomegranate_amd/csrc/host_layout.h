@@ -134,6 +134,26 @@ struct req_layout {
     size_t o_pack, o_hrec;      /* device, host: the packed records */
 };
 
+/* The ITB check.  The walks' partition and inputs, with 32 bytes of header
+ * facts per block among them; the decoders' two words lie among the inputs
+ * (a stored block's are staged).  The results -- the three per-block words,
+ * then the 48-byte reports, then the masks when the caller asked for them --
+ * lie alike on both sides (device o_res, host o_hres) outside the inputs, so
+ * that nothing of them is uploaded, and come back in one copy; the r_ offsets
+ * are relative to their start.  The kernels' status and out_len are copied
+ * into the results on the device. */
+struct itb_check_layout {
+    struct scan_layout scan;
+    size_t o_hdr;               /* struct pom_check_hdr per block */
+    size_t o_res, o_hres;
+    size_t r_status, r_outlen;  /* i32, u32 per block: adjacent, in this order */
+    size_t r_err;               /* i32 per block */
+    size_t r_report;            /* 48 bytes per block, 8-byte aligned */
+    size_t r_smask, r_imask;    /* 256 and 128 bytes per block, when masks != 0 */
+    size_t res_bytes;
+    int masks;
+};
+
 struct layout {
     size_t nb;
     const size_t *ids;
@@ -153,6 +173,7 @@ struct layout {
         struct gcstat_layout gcstat;    /* (starts with the walk's) */
         struct col_layout col;
         struct req_layout req;
+        struct itb_check_layout check;
     } u;
 };
 
@@ -175,6 +196,10 @@ void pom_layout_col(struct layout *L, const size_t *ids, size_t nb, const size_t
 void pom_layout_req(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
                     const size_t *cap, const struct req_spec *Q, size_t nreq, size_t blob_bytes, int records,
                     size_t scratch);
+
+/* masks != 0: the results have room for the slot and ITE masks */
+void pom_layout_check(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, int masks, size_t scratch);
 
 /* The staging of a group of k single calls (host_single.c).  The header
  * arrays, then the inputs, lie alike on both sides and go up in one H2D copy

@@ -9,9 +9,10 @@
  * (gc_merge.hip) and the merged map in the records' place; the column
  * read (col_slice.hip), the lookup (itb_find.hip) and the key/value get
  * (itb_kvget.hip) carry requests, the last two as one operation told apart by
- * a descriptor (struct req_spec) and their kernels.  Their callers (gc_scan.c,
- * gc_stat.c, readdir.c, kvlist.c, column_codec.c, lookup.c, kvget.c) select the blocks
- * and put the results in the caller's order.
+ * a descriptor (struct req_spec) and their kernels; the ITB check
+ * (itb_check.hip) has the walks' partition and fixed-size results.  Their
+ * callers (gc_scan.c, gc_stat.c, readdir.c, kvlist.c, column_codec.c, lookup.c,
+ * kvget.c, check.c) select the blocks and put the results in the caller's order.
  */
 #include <pthread.h>
 #include <stdlib.h>
@@ -21,6 +22,7 @@
 #include "host_requests.h"
 #include "lzo_mi355x.h"
 #include "minilzo.h"
+#include "pom_check.h"
 #include "pom_column.h"
 #include "pom_gc.h"
 #include "pom_kvget.h"
@@ -782,4 +784,123 @@ int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t 
 int pom_kvget_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks, struct pom_req_sink *sink)
 {
     return req_batch(&kg_ops, src, src_len, nblocks, sink);
+}
+
+/* ------------------------------------------------------------------------ */
+/* The ITB check: decode, check (itb_check.hip), reports back                 */
+/* ------------------------------------------------------------------------ */
+/* The walks' partition (LZO records first, stored ones checked as staged)
+ * without their record room: every result has a fixed size, so one copy of a
+ * size known at the launch brings everything back, queued once the chunk's
+ * kernels are done (the column reads say why).  Staging (host and device alike
+ * up to the inputs' end; pom_layout_check):
+ *   [src_off u64][dst_off u64][scan_off u64][header facts, 32 bytes per block]
+ *   [src_len u32][dst_cap u32][status i32][out_len u32][adepth u8]
+ *   [src bytes, 16-B aligned per block]
+ *   device: [decoded payloads][decoder scratch]
+ *   both:   [status i32][out_len u32][err i32][reports, 48 bytes per block]
+ *           [slot masks, 256 per block][ITE masks, 128 per block]      <- D2H, one copy
+ * The masks have room only when the caller asked for them.  The decoders'
+ * status and out_len are copied into the results on the device, so that
+ * nothing of the results is uploaded.  No decoded byte leaves the device. */
+static size_t ck_cap(const struct hbatch *B, size_t b)
+{
+    const struct pom_check_sink *C = B->sink;
+    return C->cap[b];
+}
+
+static int ck_masks(const struct pom_check_sink *C)
+{
+    return C->slot_mask != NULL || C->ite_mask != NULL;
+}
+
+/* the chunk budget counts the header facts and the results */
+static size_t ck_extra_cost(const struct hbatch *B, size_t b)
+{
+    (void)b;
+    return sizeof(struct pom_check_hdr) + 12 + sizeof(struct pom_check_report) +
+           (ck_masks(B->sink) ? 8 * (POM_CK_SLOT_MASK_WORDS + POM_CK_ITE_MASK_WORDS) : 0);
+}
+
+static void ck_unreached(const struct hbatch *B, size_t b)
+{
+    const struct pom_check_sink *C = B->sink;
+    C->err[b] = LZO_E_ERROR;
+}
+
+static void ck_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    pom_layout_check(L, ids, nb, nlzo, B->src_len, B->cap, ck_masks(B->sink),
+                     lzo_mi355x_decompress_scratch((uint32_t)nlzo));
+}
+
+static int ck_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    const struct pom_check_sink *C = B->sink;
+    struct pom_check_hdr *hd = (struct pom_check_hdr *)(h + L->u.check.o_hdr);
+    pom_stage_inputs(L, h, B);
+    stage_scan(L, &L->u.check.scan, h, C->adepth);
+    for (size_t i = 0; i < L->nb; i++)
+        hd[i] = C->hdr[L->ids[i]];
+    return 0;
+}
+
+static int ck_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct pom_check_sink *C = B->sink;
+    const struct itb_check_layout *K = &L->u.check;
+    uint8_t *d = S->dmem, *res = d + K->o_res;
+    if (pom_decode_lzo_blocks(S, L, 0) != 0)
+        return -1;
+    if (lzo_mi355x_launch_itb_check(d, (const uint64_t *)(d + K->scan.o_scanoff), (const uint32_t *)(d + L->o_outlen),
+                                    (const int32_t *)(d + L->o_status), d + K->scan.o_adepth,
+                                    (const struct pom_check_hdr *)(d + K->o_hdr), (uint32_t)L->nb, C->flags,
+                                    (struct pom_check_report *)(res + K->r_report),
+                                    K->masks ? (uint64_t *)(res + K->r_smask) : NULL,
+                                    K->masks ? (uint64_t *)(res + K->r_imask) : NULL, (int32_t *)(res + K->r_err),
+                                    S->stream) != 0)
+        return -1;
+    /* status, then out_len: adjacent among the inputs and among the results */
+    return hipMemcpyAsync(res + K->r_status, d + L->o_status, 8 * L->nb, hipMemcpyDeviceToDevice, S->stream) ==
+                   hipSuccess ? 0 : -1;
+}
+
+static int ck_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
+{
+    (void)B;
+    return results_back(S, L->u.check.o_hres, L->u.check.o_res, L->u.check.res_bytes, packed);
+}
+
+static int ck_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct pom_check_sink *C = B->sink;
+    const struct itb_check_layout *K = &L->u.check;
+    const uint8_t *res = S->hmem + K->o_hres;
+    const int32_t *st = (const int32_t *)(res + K->r_status), *er = (const int32_t *)(res + K->r_err);
+    const uint32_t *ol = (const uint32_t *)(res + K->r_outlen);
+    for (size_t i = 0; i < L->nb; i++) {
+        const size_t b = L->ids[i], to = C->idx[b];
+        C->status[b] = st[i];
+        C->out_len[b] = ol[i];
+        C->err[b] = er[i];
+        memcpy(&C->report[to], res + K->r_report + sizeof(struct pom_check_report) * i, sizeof(struct pom_check_report));
+        if (C->slot_mask)
+            memcpy(C->slot_mask + POM_CK_SLOT_MASK_WORDS * to, res + K->r_smask + 8 * POM_CK_SLOT_MASK_WORDS * i,
+                   8 * POM_CK_SLOT_MASK_WORDS);
+        if (C->ite_mask)
+            memcpy(C->ite_mask + POM_CK_ITE_MASK_WORDS * to, res + K->r_imask + 8 * POM_CK_ITE_MASK_WORDS * i,
+                   8 * POM_CK_ITE_MASK_WORDS);
+    }
+    return 0;
+}
+
+static const struct chunk_ops ck_ops = {"itb check", 0, ck_cap, ck_extra_cost, ck_unreached, ck_layout,
+                                        ck_stage, ck_kernels, ck_collect, ck_unpack};
+
+int pom_itb_check_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                          struct pom_check_sink *sink)
+{
+    struct hbatch B = {.ops = &ck_ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
+                       .sink = sink};
+    return pom_host_batch(&B, nblocks);
 }

@@ -334,6 +334,39 @@ int pom_lookup_chunked(const uint8_t *const *src, const size_t *src_len, size_t 
 int pom_kvget_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                       struct pom_req_sink *sink);
 
+/* The ITB check (itb_check.hip): pom_itb_check_dev of include/pom_check.h, one
+ * launch on `stream`; flags are the caller's to refuse. */
+struct pom_check_hdr;
+struct pom_check_report;
+int lzo_mi355x_launch_itb_check(const uint8_t *payload, const uint64_t *payload_off,
+                                const uint32_t *payload_len, const int32_t *status,
+                                const uint8_t *adepth, const struct pom_check_hdr *hdr, uint32_t nitb,
+                                uint32_t flags, struct pom_check_report *report, uint64_t *slot_mask,
+                                uint64_t *ite_mask, int32_t *err, hipStream_t stream);
+
+/* Host side (host_records.c), not part of the ABI: pom_gc_scan_chunked's
+ * pipeline (LZO records decoded, stored ones checked as staged) with the check
+ * behind each chunk's decode.  Block k of the call is the caller's record
+ * idx[k]: its report, and its masks when the caller gave arrays for them, go
+ * straight to their places in the caller's order, the per-block words to
+ * status[k], out_len[k] and err[k].  A block whose chunk is not delivered reads
+ * err LZO_E_ERROR.  Only 32 bytes of header facts go up besides the payloads,
+ * and only the three words, the reports and the masks come back. */
+struct pom_check_sink {
+    const uint8_t *is_lzo;
+    const size_t *cap;
+    const uint8_t *adepth;
+    const struct pom_check_hdr *hdr;    /* per block */
+    const size_t *idx;
+    uint32_t flags;
+    int32_t *status, *err;
+    uint32_t *out_len;
+    struct pom_check_report *report;    /* the caller's, in the caller's order */
+    uint64_t *slot_mask, *ite_mask;     /* the caller's, or NULL */
+};
+int pom_itb_check_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                          struct pom_check_sink *sink);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,8 @@ EXPORTS = (
     "pom_kvlist_dev", "pom_kvlist_batch",
     # include/pom_kvget.h
     "pom_kvget_dev", "pom_kvget_batch",
+    # include/pom_check.h
+    "pom_itb_check_dev", "pom_itb_check_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
