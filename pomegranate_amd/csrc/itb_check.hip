@@ -45,7 +45,9 @@ namespace {
 constexpr uint32_t kWave = 64;
 constexpr uint32_t kCheckThreads = 256;
 constexpr uint32_t kCheckWaves = kCheckThreads / kWave;
-constexpr uint32_t kCheckGridMax = 4096;            // then a grid stride
+// then a grid stride: a workgroup takes ITB b, b + 4096, ... in the same LDS
+// (tests/test_gpu_check.py test_dev_many_itbs_reuse_the_workgroup quotes the 4096)
+constexpr uint32_t kCheckGridMax = 4096;
 constexpr uint32_t kSlotWords = POM_CK_SLOT_MASK_WORDS, kIteWords = POM_CK_ITE_MASK_WORDS;
 
 // slot bitmaps beyond kinds 0 ... 11

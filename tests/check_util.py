@@ -9,6 +9,7 @@ itb_del_ite and __ite_unlink (:567-671)."""
 from __future__ import annotations
 
 import struct
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -380,18 +381,68 @@ def random_table(seed: int, adepth: int, steps: int, depth: int = 0, itbid: int 
 
 
 # ---------------------------------------------------------------------------
-# One hand-made table per kind, at adepth 2 (d = 4: slots 0 ... 7 in use)
+# One hand-made table per kind.  kind_tables() is the table set at adepth 2
+# (d = 4: slots 0 ... 7 in use) the first tests were written on;
+# kind_tables(adepth, where) puts the same defects at the low or the high end
+# of every range an adepth has.
 # ---------------------------------------------------------------------------
 BASE_DEPTH, BASE_ITBID = 2, 1
+WHERES = ("low", "high")
+# the cases that need a third ITE or a third overflow slot: not at adepth 1 (2 ITEs, 4 slots)
+KIND_CASES_NEED_THREE = ("entry_dead_orphan", "shared_misfiled", "leaked", "island", "leaked_island", "orphan")
 
 
-def base_table() -> Table:
-    """ITE 0 (hash 1) in home slot 1, ITE 1 (hash 5) behind it in overflow slot
-    4: slot 1 = (0, 4, CONFLICT), slot 4 = (1, -, UNIQUE).  Both hashes carry
-    itbid 1 at depth 2.  Home slots 0, 2, 3 and ITEs 2, 3 are free."""
-    t = Table(2, 42, BASE_DEPTH, BASE_ITBID)
-    assert (t.add(1 | BASE_ITBID << 10), t.add(5 | BASE_ITBID << 10)) == (0, 1)
-    assert get_slot(t.rec, H, 1) == (0, 4, IDX_CONFLICT) and get_slot(t.rec, H, 4)[::2] == (1, IDX_UNIQUE)
+class Places:
+    """Where a hand-made table sits.  e: the base chain's two ITEs, then two
+    spare ones; hb: the base chain's home slot, hx: a spare home slot; o: the
+    base chain's overflow slot, the next one (kept free: link_free's target),
+    then two spare ones.
+      low   ITEs 0, 1, 2, 3; home slots 1 and 0; overflow slots d, d + 1, ...
+      high  ITEs d - 2, d - 1, d - 3, d - 4; home slots d - 1 and d - 2;
+            overflow slots 2d - 1, 2d - 2, ...
+    At adepth 1 only e[:2] and o[:2] exist."""
+
+    def __init__(self, adepth: int, where: str):
+        assert where in WHERES and 1 <= adepth <= 10
+        d = self.d = 1 << adepth
+        if where == "low":
+            self.e, self.hb, self.hx, self.o = [0, 1, 2, 3], 1, 0, [d, d + 1, d + 2, d + 3]
+        else:
+            self.e, self.hb, self.hx = [d - 2, d - 1, d - 3, d - 4], d - 1, d - 2
+            self.o = [2 * d - 1, 2 * d - 2, 2 * d - 3, 2 * d - 4]
+        if adepth == 1:
+            self.e, self.o = self.e[:2], self.o[:2]
+
+
+def base_table(adepth: int = 2, where: str = "low") -> Table:
+    """ITE e0 (hash hb) in home slot hb, ITE e1 (hash hb + d) behind it in
+    overflow slot o0: slot hb = (e0, o0, CONFLICT), slot o0 = (e1, -, UNIQUE)
+    (Places).  Both hashes carry itbid 1 at depth 2.  Nothing else is in use.
+    At adepth 2, low: ITE 0 (hash 1) in home slot 1, ITE 1 (hash 5) in overflow
+    slot 4.  A low table is built by Table.add; a high one by hand, with the
+    header add would leave had the MDS filled the ITEs from the top, and its
+    payload holds all d ITEs."""
+    t = Table(adepth, 42, BASE_DEPTH, BASE_ITBID)
+    at, d = Places(adepth, where), 1 << adepth
+    h0, h1 = at.hb | BASE_ITBID << 10, (at.hb + d) | BASE_ITBID << 10
+    if where == "low":
+        assert (t.add(h0), t.add(h1)) == (0, 1)
+    else:
+        for nr, hsh in ((at.e[0], h0), (at.e[1], h1)):
+            t._bit(nr, 1)
+            ite = H + ITE_OFF + ITE_SIZE * nr
+            t.rec[ite: ite + ITE_SIZE] = t.rng.integers(0, 256, ITE_SIZE, dtype=np.uint8).tobytes()
+            set_hash(t.rec, nr, hsh)
+            t.hashes[nr] = hsh
+        set_slot(t.rec, H, at.hb, at.e[0], at.o[0], IDX_CONFLICT)
+        set_slot(t.rec, H, at.o[0], at.e[1], 0, IDX_UNIQUE)
+        t._i32(ITBH_ENTRIES, value=2)
+        t._i32(ITBH_PSEUDO, value=1)
+        t._i32(ITBH_MAX_OFFSET, value=d - 1)
+        t._i32(ITBH_LEN, value=ITB_SIZE + ITE_SIZE * d)
+        struct.pack_into("<HH", t.rec, ITBH_INF, d, 1)
+    assert get_slot(t.rec, H, at.hb) == (at.e[0], at.o[0], IDX_CONFLICT)
+    assert get_slot(t.rec, H, at.o[0])[::2] == (at.e[1], IDX_UNIQUE)
     return t
 
 
@@ -404,7 +455,7 @@ def _live(t: Table, nr: int, hsh: int):
                                                   ITB_SIZE + ITE_SIZE * (nr + 1)))
 
 
-def kind_tables():
+def kind_tables(adepth: int = 2, where: str = "low"):
     """name -> (record, {kind: count}, slot bits, ITE bits): what a check with
     hdr NULL must report, exactly.  Three kinds cannot stand alone:
       S_SHARED  needs two good links into one overflow slot t.  If both come
@@ -419,38 +470,62 @@ def kind_tables():
     unreached cycle, where every slot has indeg 1.  The usual damage, a chain
     cut off its home slot, gives both: the head leaked, the rest an island.
     S_ENTRY_DEAD alone is a cleared bitmap bit; a slot whose entry was
-    redirected to a dead ITE leaves its old ITE an orphan as well."""
+    redirected to a dead ITE leaves its old ITE an orphan as well.
+
+    The ITEs and slots are Places(adepth, where)'s, and a defect's value sits
+    at the edge of its range as well: outside slots 2d and 2047, stray bits d
+    and 1023, entry d (low) or 32767 (high), conflict 2d or 32767 out of range
+    and 0 or d - 1 into the home half.  At adepth 10 no slot lies outside and
+    no bit is stray: those two tables are the valid one.  At adepth 1 the
+    KIND_CASES_NEED_THREE are absent."""
     out = {}
+    at, d = Places(adepth, where), 1 << adepth
+    low = where == "low"
+    e, o, hb, hx = at.e + [None] * 2, at.o + [None] * 2, at.hb, at.hx
+    tag = BASE_ITBID << 10
 
     def case(name, kinds, slots=(), ites=()):
         def deco(fn):
-            t = base_table()
+            if adepth == 1 and name in KIND_CASES_NEED_THREE:
+                return
+            t = base_table(adepth, where)
             fn(t)
             out[name] = (t.record(), kinds, tuple(slots), tuple(ites))
         return deco
 
-    ss = lambda t, o, e, c, f: set_slot(t.rec, H, o, e, c, f)
+    ss = lambda t, s, entry, c, f: set_slot(t.rec, H, s, entry, c, f)
     case("valid", {})(lambda t: None)
-    case("outside", {S_OUTSIDE: 2}, (8, 2047))(lambda t: (ss(t, 8, 0, 0, IDX_UNIQUE), ss(t, 2047, 1, 4, IDX_CONFLICT)))
-    case("flag", {S_FLAG: 1}, (1,))(lambda t: ss(t, 1, 0, 4, IDX_OVERFLOW))
-    case("link_range", {S_LINK_RANGE: 1}, (4,))(lambda t: ss(t, 4, 1, 8, IDX_CONFLICT))
-    case("link_home", {S_LINK_HOME: 1}, (4,))(lambda t: ss(t, 4, 1, 0, IDX_CONFLICT))
-    case("link_free", {S_LINK_FREE: 1}, (4,))(lambda t: ss(t, 4, 1, 5, IDX_CONFLICT))
-    case("entry_range", {S_ENTRY_RANGE: 1}, (4,))(lambda t: (ss(t, 4, 4, 0, IDX_UNIQUE), t._bit(1, 0)))
-    case("entry_dead", {S_ENTRY_DEAD: 1}, (4,))(lambda t: t._bit(1, 0))
-    case("entry_dead_orphan", {S_ENTRY_DEAD: 1, E_ORPHAN: 1}, (4,), (1,))(lambda t: ss(t, 4, 2, 0, IDX_UNIQUE))
-    case("shared_loop", {S_SHARED: 1, S_LOOP: 1}, (1, 4))(lambda t: ss(t, 4, 1, 4, IDX_CONFLICT))
-    case("shared_misfiled", {S_SHARED: 1, S_MISFILED: 1}, (4,))(
-        lambda t: (_live(t, 2, 0), ss(t, 0, 2, 4, IDX_CONFLICT)))
-    case("leaked", {S_LEAKED: 1}, (6,))(lambda t: (_live(t, 2, 2), ss(t, 6, 2, 0, IDX_UNIQUE)))
-    case("island", {S_ISLAND: 1}, (6,))(lambda t: (_live(t, 2, 2), ss(t, 6, 2, 6, IDX_CONFLICT)))
-    case("leaked_island", {S_LEAKED: 1, S_ISLAND: 1}, (6, 7))(
-        lambda t: (_live(t, 2, 2), _live(t, 3, 2), ss(t, 6, 2, 7, IDX_CONFLICT), ss(t, 7, 3, 0, IDX_UNIQUE)))
-    case("misfiled_home", {S_MISFILED: 1}, (1,))(lambda t: set_hash(t.rec, 0, 2 | BASE_ITBID << 10))
-    case("misfiled_over", {S_MISFILED: 1}, (4,))(lambda t: set_hash(t.rec, 1, 4 | BASE_ITBID << 10))
-    case("stray", {E_STRAY: 2}, (), (4, 1023))(lambda t: (t._bit(4, 1), t._bit(1023, 1)))
-    case("dup", {E_DUP: 1}, (), (0,))(lambda t: (ss(t, 4, 0, 0, IDX_UNIQUE), t._bit(1, 0)))
-    case("orphan", {E_ORPHAN: 1}, (), (2,))(lambda t: _live(t, 2, 3))
+    if adepth < 10:
+        case("outside", {S_OUTSIDE: 2}, (2 * d, 2047))(
+            lambda t: (ss(t, 2 * d, e[0], 0, IDX_UNIQUE), ss(t, 2047, e[1], o[0], IDX_CONFLICT)))
+    else:
+        case("outside", {})(lambda t: None)
+    case("flag", {S_FLAG: 1}, (hb,))(lambda t: ss(t, hb, e[0], o[0], IDX_OVERFLOW))
+    case("link_range", {S_LINK_RANGE: 1}, (o[0],))(lambda t: ss(t, o[0], e[1], 2 * d if low else 32767, IDX_CONFLICT))
+    case("link_home", {S_LINK_HOME: 1}, (o[0],))(lambda t: ss(t, o[0], e[1], 0 if low else d - 1, IDX_CONFLICT))
+    case("link_free", {S_LINK_FREE: 1}, (o[0],))(lambda t: ss(t, o[0], e[1], o[1], IDX_CONFLICT))
+    case("entry_range", {S_ENTRY_RANGE: 1}, (o[0],))(
+        lambda t: (ss(t, o[0], d if low else 32767, 0, IDX_UNIQUE), t._bit(e[1], 0)))
+    case("entry_dead", {S_ENTRY_DEAD: 1}, (o[0],))(lambda t: t._bit(e[1], 0))
+    case("entry_dead_orphan", {S_ENTRY_DEAD: 1, E_ORPHAN: 1}, (o[0],), (e[1],))(
+        lambda t: ss(t, o[0], e[2], 0, IDX_UNIQUE))
+    case("shared_loop", {S_SHARED: 1, S_LOOP: 1}, (hb, o[0]))(lambda t: ss(t, o[0], e[1], o[0], IDX_CONFLICT))
+    case("shared_misfiled", {S_SHARED: 1, S_MISFILED: 1}, (o[0],))(
+        lambda t: (_live(t, e[2], hx), ss(t, hx, e[2], o[0], IDX_CONFLICT)))
+    case("leaked", {S_LEAKED: 1}, (o[2],))(lambda t: (_live(t, e[2], 2), ss(t, o[2], e[2], 0, IDX_UNIQUE)))
+    case("island", {S_ISLAND: 1}, (o[2],))(lambda t: (_live(t, e[2], 2), ss(t, o[2], e[2], o[2], IDX_CONFLICT)))
+    case("leaked_island", {S_LEAKED: 1, S_ISLAND: 1}, (o[2], o[3]))(
+        lambda t: (_live(t, e[2], 2), _live(t, e[3], 2), ss(t, o[2], e[2], o[3], IDX_CONFLICT),
+                   ss(t, o[3], e[3], 0, IDX_UNIQUE)))
+    # the hash moves to another home slot's low bits (hb is 1 or d - 1)
+    case("misfiled_home", {S_MISFILED: 1}, (hb,))(lambda t: set_hash(t.rec, e[0], (2 if low else hb - 1) | tag))
+    case("misfiled_over", {S_MISFILED: 1}, (o[0],))(lambda t: set_hash(t.rec, e[1], d | tag))
+    if adepth < 10:
+        case("stray", {E_STRAY: 2}, (), (d, 1023))(lambda t: (t._bit(d, 1), t._bit(1023, 1)))
+    else:
+        case("stray", {})(lambda t: None)
+    case("dup", {E_DUP: 1}, (), (e[0],))(lambda t: (ss(t, o[0], e[0], 0, IDX_UNIQUE), t._bit(e[1], 0)))
+    case("orphan", {E_ORPHAN: 1}, (), (e[2],))(lambda t: _live(t, e[2], 3))
     return out
 
 
@@ -502,3 +577,199 @@ def fuzzed(seed: int, adepth: "int | None" = None):
             (v,) = struct.unpack_from("<H", rec, off)
             struct.pack_into("<H", rec, off, (v + int(rng.integers(-1, 2)) * int(rng.choice([1, d]))) & 0xFFFF)
     return rec, adepth
+
+
+# ---------------------------------------------------------------------------
+# Directed tables: each aims at one piece of the kernel's machinery -- a word
+# or half boundary, the once / twice bitmaps, the walk's bound -- and states in
+# closed form what the check must report, so the oracle above is judged too.
+# ---------------------------------------------------------------------------
+class Directed(NamedTuple):
+    """A table and what a check with hdr NULL must report for it: count[k] for
+    every kind 0 ... 14 (a kind not named counts 0), exactly the slot-mask and
+    ITE-mask bits, and `reached` and `longest` where the builder states them
+    (None: not stated)."""
+    name: str
+    rec: bytearray
+    adepth: int
+    kinds: dict
+    slots: tuple
+    ites: tuple
+    reached: Optional[int] = None
+    longest: Optional[int] = None
+
+
+def assert_directed(t: Directed, err, report, slot_mask=None, ite_mask=None):
+    """The closed-form values of t against one result (the masks where the
+    call returned them)."""
+    f = report_fields(report)
+    assert int(err) == 0, (t.name, int(err))
+    assert f["count"][:15] == [t.kinds.get(k, 0) for k in range(15)], (t.name, f)
+    assert f["findings"] & 0x7FFF == sum(1 << k for k, c in t.kinds.items() if c), (t.name, f)
+    if slot_mask is not None:
+        assert [int(w) for w in slot_mask] == masks_of(t.slots, 32), (t.name, "slot mask")
+    if ite_mask is not None:
+        assert [int(w) for w in ite_mask] == masks_of(t.ites, 16), (t.name, "ITE mask")
+    if t.reached is not None:
+        assert f["reached"] == t.reached, (t.name, f)
+    if t.longest is not None:
+        assert f["longest"] == t.longest, (t.name, f)
+
+
+def _blank(adepth: int, seed: int) -> Table:
+    """No ITE live, no slot in use; _live's hashes carry its itbid."""
+    return Table(adepth, seed, BASE_DEPTH, BASE_ITBID)
+
+
+def _comb(lo: int, hi: int):
+    """P: the first and the last bit of every 64-bit word, within [lo, hi)."""
+    return [x for x in range(lo, hi) if x % 64 in (0, 63)]
+
+
+def slot_comb(adepth: int) -> Directed:
+    """Findings at the first and last slot of every word of both halves
+    (adepth 6 ... 10: d is a multiple of 64).  A home slot of P is CONFLICT
+    with its own live ITE (hash: its number) and links to a free overflow slot
+    outside P: S_LINK_FREE.  An overflow slot of P is UNIQUE with an entry at
+    or above d and no link into it: S_ENTRY_RANGE and S_LEAKED."""
+    assert 6 <= adepth <= 10
+    t, d = _blank(adepth, 600 + adepth), 1 << adepth
+    home, over = _comb(0, d), _comb(d, 2 * d)
+    for h in home:
+        _live(t, h, h)
+        set_slot(t.rec, H, h, h, d + (h + 2) % d, IDX_CONFLICT)         # (h + 2) % 64 is 2 or 1
+    for i, s in enumerate(over):
+        set_slot(t.rec, H, s, d if i % 2 == 0 else 32767, 0, IDX_UNIQUE)
+    kinds = {S_LINK_FREE: len(home), S_ENTRY_RANGE: len(over), S_LEAKED: len(over)}
+    return Directed(f"slot_comb@{adepth}", t.record(), adepth, kinds, tuple(home + over), (), len(home), 1)
+
+
+def ite_comb(adepth: int) -> Directed:
+    """No slot in use; the bitmap is P: the bits below d are E_ORPHAN, those
+    from d up E_STRAY (none at adepth 10)."""
+    assert 6 <= adepth <= 10
+    t, d = _blank(adepth, 610 + adepth), 1 << adepth
+    for nr in _comb(0, d):
+        _live(t, nr, nr)
+    for nr in _comb(d, 1024):
+        t._bit(nr, 1)
+    kinds = {E_ORPHAN: len(_comb(0, d)), E_STRAY: len(_comb(d, 1024))}
+    return Directed(f"ite_comb@{adepth}", t.record(), adepth, kinds, (), tuple(_comb(0, 1024)), 0, 0)
+
+
+def alternating(adepth: int) -> Directed:
+    """indeg 2 beside indeg 1, all along the overflow half: for j = 0, 1, ...
+    while 3j + 2 < d, home slots 3j and 3j + 1 link to overflow slot d + 2j and
+    home slot 3j + 2 to d + 2j + 1.  Home slot h holds live ITE h (hash h);
+    d + 2j holds ITE 3j again and d + 2j + 1 ITE 3j + 2, both UNIQUE.  So the
+    even overflow slots are S_SHARED, and S_MISFILED too (two home slots reach
+    them); the odd ones are neither; ITEs 3j and 3j + 2 are E_DUP."""
+    assert 2 <= adepth <= 10
+    t, d = _blank(adepth, 620 + adepth), 1 << adepth
+    js = [j for j in range(d) if 3 * j + 2 < d]
+    for j in js:
+        for h, target in ((3 * j, d + 2 * j), (3 * j + 1, d + 2 * j), (3 * j + 2, d + 2 * j + 1)):
+            _live(t, h, h)
+            set_slot(t.rec, H, h, h, target, IDX_CONFLICT)
+        set_slot(t.rec, H, d + 2 * j, 3 * j, 0, IDX_UNIQUE)
+        set_slot(t.rec, H, d + 2 * j + 1, 3 * j + 2, 0, IDX_UNIQUE)
+    even = tuple(d + 2 * j for j in js)
+    kinds = {S_SHARED: len(js), S_MISFILED: len(js), E_DUP: 2 * len(js)}
+    dup = tuple(nr for j in js for nr in (3 * j, 3 * j + 2))
+    return Directed(f"alternating@{adepth}", t.record(), adepth, kinds, even, dup, 5 * len(js), 2)
+
+
+def star(adepth: int) -> Directed:
+    """indeg d on one slot: every home slot h (live ITE h, hash h) links to
+    overflow slot d, UNIQUE with entry 0."""
+    t, d = _blank(adepth, 630 + adepth), 1 << adepth
+    for h in range(d):
+        _live(t, h, h)
+        set_slot(t.rec, H, h, h, d, IDX_CONFLICT)
+    set_slot(t.rec, H, d, 0, 0, IDX_UNIQUE)
+    return Directed(f"star@{adepth}", t.record(), adepth, {S_SHARED: 1, S_MISFILED: 1, E_DUP: 1}, (d,), (0,), d + 1, 2)
+
+
+def one_ite(adepth: int) -> Directed:
+    """refs 2d on one ITE: every slot of both halves is UNIQUE with entry
+    d - 1, the only live ITE (hash d - 1).  The overflow slots are S_LEAKED,
+    the home slots other than d - 1 S_MISFILED."""
+    t, d = _blank(adepth, 640 + adepth), 1 << adepth
+    _live(t, d - 1, d - 1)
+    for s in range(2 * d):
+        set_slot(t.rec, H, s, d - 1, 0, IDX_UNIQUE)
+    kinds = {E_DUP: 1, S_LEAKED: d, S_MISFILED: d - 1}
+    return Directed(f"one_ite@{adepth}", t.record(), adepth, kinds,
+                    tuple(s for s in range(2 * d) if s != d - 1), (d - 1,), d, 1)
+
+
+CHAIN_VARIANTS = ("line", "short", "cycle", "self", "fan")
+
+
+def chain(adepth: int, variant: str, permuted: bool) -> Directed:
+    """The walk's bound.  A chain from home slot 0 (ITE 0) through the overflow
+    slots in the order o -- ascending, or a seeded permutation that does not
+    end in slot d -- where slot o[i] holds ITE o[i] - d.  Every ITE is live
+    and every hash has low bits 0, so nothing on home slot 0's chain is
+    misfiled; ITE 0 is in home slot 0 and in slot d: E_DUP.
+      line   all d overflow slots, the last UNIQUE: a path of d + 1 slots, the
+             longest a table has
+      short  one slot fewer; the ITE of o[d - 1] is E_ORPHAN
+      cycle  the last slot links back to o[0]: S_LOOP on home slot 0, S_SHARED on o[0]
+      self   the last slot links to itself: S_LOOP, S_SHARED on o[d - 1]
+      fan    the line, and every home slot h (entry h) links to o[0]: d paths
+             of d + 1 slots; o[0] is S_SHARED, every slot but home slot 0
+             S_MISFILED, every ITE E_DUP"""
+    assert variant in CHAIN_VARIANTS
+    t, d = _blank(adepth, 650 + adepth), 1 << adepth
+    o = list(range(d, 2 * d))
+    if permuted:
+        o = [int(s) for s in np.random.default_rng(0xD1CE + adepth).permutation(o)]
+        if o[-1] == d:
+            o[0], o[-1] = o[-1], o[0]
+    for nr in range(d):
+        _live(t, nr, 0)
+    set_slot(t.rec, H, 0, 0, o[0], IDX_CONFLICT)
+    m = d - 1 if variant == "short" else d
+    for i in range(m - 1):
+        set_slot(t.rec, H, o[i], o[i] - d, o[i + 1], IDX_CONFLICT)
+    back = {"cycle": o[0], "self": o[m - 1]}.get(variant)
+    set_slot(t.rec, H, o[m - 1], o[m - 1] - d, back or 0, IDX_UNIQUE if back is None else IDX_CONFLICT)
+    name = f"{variant}@{adepth}{'p' if permuted else 'a'}"
+    if variant == "line":
+        want = ({E_DUP: 1}, (), (0,), d + 1, d + 1)
+    elif variant == "short":
+        want = ({E_DUP: 1, E_ORPHAN: 1}, (), (0, o[d - 1] - d), d, d)
+    elif variant in ("cycle", "self"):
+        want = ({S_LOOP: 1, S_SHARED: 1, E_DUP: 1}, (0, back), (0,), d + 1, 0)
+    else:
+        for h in range(1, d):
+            set_slot(t.rec, H, h, h, o[0], IDX_CONFLICT)
+        want = ({S_SHARED: 1, S_MISFILED: 2 * d - 1, E_DUP: d}, tuple(range(1, 2 * d)), tuple(range(d)), 2 * d, d + 1)
+    return Directed(name, t.record(), adepth, *want)
+
+
+GROUPS = ("kinds", "combs", "counts", "walk")
+
+
+def directed(group: str, adepths=range(1, 11)):
+    """The directed tables of one group at the given adepths (where the group
+    has them):
+      kinds   kind_tables(adepth, where), low and high
+      combs   slot_comb and ite_comb, adepth 6 ... 10
+      counts  alternating (adepth 2 ... 10), star and one_ite
+      walk    chain: every variant, ascending and permuted"""
+    out = []
+    for adepth in adepths:
+        if group == "kinds":
+            for where in WHERES:
+                out += [Directed(f"{name}@{adepth}{where}", rec, adepth, kinds, slots, ites)
+                        for name, (rec, kinds, slots, ites) in kind_tables(adepth, where).items()]
+        elif group == "combs":
+            out += [slot_comb(adepth), ite_comb(adepth)] if adepth >= 6 else []
+        elif group == "counts":
+            out += ([alternating(adepth)] if adepth >= 2 else []) + [star(adepth), one_ite(adepth)]
+        else:
+            assert group == "walk"
+            out += [chain(adepth, v, p) for v in CHAIN_VARIANTS for p in (False, True)]
+    return out

@@ -2,11 +2,13 @@
 macros against the reference's structs, the rules (pomegranate_amd/csrc/
 itb_check.h, compiled as plain C++) against the Python restatement in
 check_util.py over tables built the way the MDS builds them, hand-made tables
-for every kind, fuzzed tables and the error rules; the stand-alone checkers,
-the exports, and the refusal without a GPU."""
+for every kind, fuzzed tables and the error rules; directed tables with
+closed-form answers at the word, half, count and walk edges; the stand-alone
+checkers, the exports, and the refusal without a GPU."""
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import os
 import re
 import struct
@@ -281,6 +283,112 @@ def test_one_table_per_kind(host_check):
     assert C.report_fields(got[1][0])["count"][15] == 1 and got[3][0].tolist() == C.masks_of([1], 16)
     # without hdr the flag alone turns nothing on
     assert not host_check([bytes(wrong[C.H:])], [2], None, C.CK_ITBID)[1][0][:4].any()
+
+
+# ---------------------------------------------------------------------------
+# Directed tables (check_util.directed): the closed-form answers judge the
+# oracle and itb_check.h alike
+# ---------------------------------------------------------------------------
+def directed_agree(host_check, tables):
+    """agree() over the tables, then their closed-form values against the
+    oracle's answer and against itb_check.h's with hdr NULL."""
+    recs, adepths = [t.rec for t in tables], [t.adepth for t in tables]
+    want = agree(host_check, recs, adepths)
+    bare = host_check([C.payload_of(r) for r in recs], adepths, None, 0, shift=3)
+    for b, t in enumerate(tables):
+        C.assert_directed(t, want[0][b], want[1][b], want[2][b], want[3][b])
+        C.assert_directed(t, bare[0][b], bare[1][b], bare[2][b], bare[3][b])
+        assert not bare[1][b][:4].view("<u4")[0] >> 15, t.name
+    return want
+
+
+# kind_tables(adepth, where) leaves these out: they need a third ITE or a third overflow slot
+KIND_CASES_LEFT_OUT = [
+    (1, "low", "entry_dead_orphan"), (1, "low", "shared_misfiled"), (1, "low", "leaked"), (1, "low", "island"),
+    (1, "low", "leaked_island"), (1, "low", "orphan"),
+    (1, "high", "entry_dead_orphan"), (1, "high", "shared_misfiled"), (1, "high", "leaked"), (1, "high", "island"),
+    (1, "high", "leaked_island"), (1, "high", "orphan")]
+
+
+def test_kind_tables_are_the_first_ones():
+    """kind_tables() and base_table() called as before return the bytes they
+    returned before they took an adepth and a position."""
+    h = hashlib.sha256()
+    for name, (rec, kinds, slots, ites) in C.kind_tables().items():
+        h.update(name.encode())
+        h.update(bytes(rec))
+        h.update(repr((kinds, slots, ites)).encode())
+    assert h.hexdigest() == "587b74f91d6c045f7cf2a7682d11804a635351aa790487d0f7f13412ec45d2d1"
+    assert {k: bytes(v[0]) for k, v in C.kind_tables(2, "low").items()} == \
+        {k: bytes(v[0]) for k, v in C.kind_tables().items()}
+    assert bytes(C.base_table().record()) == bytes(C.kind_tables()["valid"][0])
+
+
+@pytest.mark.parametrize("adepth", range(1, 11))
+def test_directed_kind_tables(host_check, adepth):
+    """A condition, not a measurement: one table per kind with its ITEs, slots
+    and the defect's value at the low and at the high end of their ranges.
+    Every kind 0 ... 14 appears at both positions of every adepth from 2 up;
+    at adepth 10 no slot lies outside and no bit is stray, and the two tables
+    that would show them report nothing.  What adepth 1 cannot hold is named in
+    KIND_CASES_LEFT_OUT."""
+    assert all(ad == 1 for ad, _, _ in KIND_CASES_LEFT_OUT)
+    names = list(C.kind_tables())
+    for where in C.WHERES:
+        tables = C.kind_tables(adepth, where)
+        left_out = {name for ad, wh, name in KIND_CASES_LEFT_OUT if (ad, wh) == (adepth, where)}
+        assert list(tables) == [name for name in names if name not in left_out]
+        covered = set()
+        for _, kinds, _, _ in tables.values():
+            covered |= set(kinds)
+        if adepth == 10:
+            assert tables["outside"][1] == tables["stray"][1] == {}
+            assert tables["outside"][0] == tables["stray"][0] == tables["valid"][0]
+            assert covered == set(range(15)) - {C.S_OUTSIDE, C.E_STRAY}
+        elif adepth >= 2:
+            assert covered == set(range(15))
+        if where == "high":
+            assert all(len(rec) == C.ITB_SIZE + 512 * (1 << adepth) for rec, _, _, _ in tables.values())
+    tables = C.directed("kinds", [adepth])
+    want = directed_agree(host_check, tables)
+    valid = [b for b, t in enumerate(tables) if not t.kinds]
+    assert len(valid) == (6 if adepth == 10 else 2) and not want[1][valid, :4].any()   # with the header, too
+
+
+def test_directed_combs(host_check):
+    """Findings at bit 0 and bit 63 of every word of both halves and of the ITE
+    bitmap (adepth 6 ... 10): each ballot word, and each span mask of one,
+    keeps its first and last bit and no other."""
+    tables = C.directed("combs")
+    assert [t.adepth for t in tables] == [6, 6, 7, 7, 8, 8, 9, 9, 10, 10]
+    directed_agree(host_check, tables)
+    slot, ite = tables[-2], tables[-1]
+    assert slot.kinds == {C.S_LINK_FREE: 32, C.S_ENTRY_RANGE: 32, C.S_LEAKED: 32} and len(slot.slots) == 64
+    assert ite.kinds == {C.E_ORPHAN: 32, C.E_STRAY: 0} and tables[1].kinds == {C.E_ORPHAN: 2, C.E_STRAY: 30}
+
+
+def test_directed_counts(host_check):
+    """indeg 1 beside indeg 2 along the whole overflow half, indeg d on one
+    slot, refs 2d on one ITE."""
+    tables = C.directed("counts")
+    directed_agree(host_check, tables)
+    shared = [t.kinds[C.S_SHARED] for t in tables if t.name.startswith("alternating")]
+    assert shared == [1, 2, 5, 10, 21, 42, 85, 170, 341]             # adepth 2 ... 10: one per j with 3j + 2 < d
+    assert len(tables) == 29
+
+
+def test_directed_walk(host_check):
+    """The walk's bound: a path of d + 1 slots is the longest a table has and
+    is no loop; one more good link is.  Every adepth, ascending and permuted
+    chains (1,024 walks of 1,025 slots in the adepth-10 fan)."""
+    tables = C.directed("walk")
+    assert len(tables) == 100
+    want = directed_agree(host_check, tables)
+    for b, t in enumerate(tables):
+        d, f = 1 << t.adepth, C.report_fields(want[1][b])
+        variant = t.name.split("@")[0]
+        assert (f["longest"], f["count"][C.S_LOOP]) == {"line": (d + 1, 0), "short": (d, 0), "cycle": (0, 1),
+                                                        "self": (0, 1), "fan": (d + 1, 0)}[variant], t.name
 
 
 def test_funnel(host_check):

@@ -1,16 +1,20 @@
 """GPU: the ITB check (include/pom_check.h) against the Python restatement of
 its rules in check_util.py -- pom_itb_check_dev on one guarded arena,
 pom_itb_check_batch through the host chunk pipeline.  err, all 48 bytes of
-every report and both masks are compared."""
+every report and both masks are compared; the directed tables
+(check_util.directed) also carry closed-form answers."""
 from __future__ import annotations
 
 import ctypes
+import os
+import re
 import struct
 
 import numpy as np
 import pytest
 
 import check_util as C
+from conftest import ROOT
 from gpu_util import guarded_batch
 from pomegranate_amd import check, itb, lzo
 
@@ -124,10 +128,13 @@ class Outputs:
                 cut("ite_mask").view(np.uint64).reshape(self.n, 16) if masks else None)
 
 
-def check_dev_once(dev, payloads, adepths, hdrs, flags, shift=0, masks=True, status=None):
+def check_dev_once(dev, payloads, adepths, hdrs, flags, shift=0, masks=True, status=None, src=None):
+    """src: the caller's own batch of the payloads (its offsets may repeat) in
+    place of one guarded batch of them at residues from `shift`."""
     n = len(payloads)
-    src = guarded_batch(torch, [bytes(p) for p in payloads], dev, [(shift + 3 * b) % 16 if shift else 0
-                                                                   for b in range(n)], fill=0xEE)
+    if src is None:
+        src = guarded_batch(torch, [bytes(p) for p in payloads], dev, [(shift + 3 * b) % 16 if shift else 0
+                                                                       for b in range(n)], fill=0xEE)
     adepth = torch.tensor(adepths, dtype=torch.uint8, device=dev)
     st = None if status is None else torch.tensor(status, dtype=torch.int32, device=dev)
     hd = None
@@ -196,6 +203,108 @@ def test_dev_refuses_other_flags(dev, tables):
         check_dev_once(dev, [C.payload_of(recs[0])], adepths[:1], hdrs[:1], 2)
     with pytest.raises(ValueError):
         check_dev_once(dev, [C.payload_of(recs[0])], adepths[:1], hdrs[:1], C.CK_ITBID | 0x80000000)
+
+
+# ---------------------------------------------------------------------------
+# Directed tables: the kernel's words, halves, once / twice bitmaps, walk bound
+# and its reuse of one workgroup's LDS
+# ---------------------------------------------------------------------------
+_directed_cache = {}
+
+
+def directed_tables(group):
+    """(tables, payloads, hdrs, the oracle's answer with hdr and POM_CK_ITBID),
+    built once per group."""
+    if group not in _directed_cache:
+        tables = C.directed(group)
+        payloads = [C.payload_of(t.rec) for t in tables]
+        hdrs = [C.hdr_of(t.rec) for t in tables]
+        want = C.expect(payloads, [t.adepth for t in tables], hdrs, C.CK_ITBID)
+        for b, t in enumerate(tables):                                  # the oracle is judged too
+            C.assert_directed(t, want[0][b], want[1][b], want[2][b], want[3][b])
+        _directed_cache[group] = (tables, payloads, hdrs, want)
+    return _directed_cache[group]
+
+
+@pytest.mark.parametrize("group", C.GROUPS)
+def test_dev_directed(dev, group):
+    """One call per group and shift (0: every payload aligned; 5: residues of
+    their own), with masks, the header facts and POM_CK_ITBID: the kernel
+    equals the oracle in err, report and masks, and both state the closed-form
+    values the builders give.
+      kinds   a table per kind at adepth 1 ... 10, its slots, ITEs and values
+              at the low and the high end of their ranges: every ballot word
+              and span mask from word 0 to the last, d and 2d mid-word and on
+              word edges
+      combs   bit 0 and bit 63 of every word
+      counts  indeg 1 beside indeg 2, indeg d on one bit, refs 2d on one bit
+      walk    paths of d + 1 slots (legal) and their loops, 1,024 lanes on
+              1,025 slots each in the adepth-10 fan"""
+    tables, payloads, hdrs, want = directed_tables(group)
+    adepths = [t.adepth for t in tables]
+    for shift in (0, 5):
+        got = check_dev_once(dev, payloads, adepths, hdrs, C.CK_ITBID, shift)
+        same(got, want)
+        for b, t in enumerate(tables):
+            C.assert_directed(t, got[0][b], got[1][b], got[2][b], got[3][b])
+
+
+GRID_MAX = 4096                 # itb_check.hip kCheckGridMax: above it a workgroup takes ITB b, b + 4096, ...
+
+
+def test_dev_many_itbs_reuse_the_workgroup(dev):
+    """2 * 4096 + 37 ITBs over 8 distinct payloads (payload_off repeats), so
+    that every workgroup checks two or three ITBs in the LDS it never clears
+    as a whole: a full table before an empty one, an error's early `continue`
+    before and after a checked table, 1,024 stale hash words before a table of
+    two ITEs.  Every ordered pair of the 8 kinds, equal pairs included, meets
+    in one workgroup.  All results are compared (the outputs' guards with them);
+    the second call has no header facts and no masks."""
+    n = 2 * GRID_MAX + 37
+    with open(os.path.join(ROOT, "pomegranate_amd", "csrc", "itb_check.hip")) as f:
+        assert re.search(r"kCheckGridMax = (\d+);", f.read()).group(1) == str(GRID_MAX)
+    t = C.random_table(9, 3, 40)
+    cut = C.payload_of(t.record())[: C.ITE_OFF + C.ITE_SIZE * (max(t.hashes) + 1) - 1]
+    empty = C.Table(10).record()
+    tables = C.kind_tables()
+    fan = C.chain(6, "fan", True)
+    #            record or payload, adepth, status
+    kinds = [(C.funnel(), 10, 0),
+             (empty, 10, 0),
+             (C.random_table(51, 1, 30, depth=2, itbid=3).record(), 1, 0),
+             (tables["leaked_island"][0], 2, 0),
+             (cut, 3, 0),
+             (tables["valid"][0], 0, 0),
+             (tables["dup"][0], 2, -6),
+             (fan.rec, 6, 0)]
+    payloads = [k[0] if isinstance(k[0], bytes) else C.payload_of(k[0]) for k in kinds]
+    assert len(payloads[1]) == C.ITE_OFF and len(set(payloads)) == 8
+    hdr8 = [C.hdr_of(t.record()) if isinstance(k[0], bytes) else C.hdr_of(k[0]) for k in kinds]
+
+    def kind(b):
+        return b % 8 if b < GRID_MAX else (b - GRID_MAX) // 8 % 8 if b < 2 * GRID_MAX else (b + 3) % 8
+    which = np.array([kind(b) for b in range(n)])
+    # workgroup g takes ITBs g, g + 4096 (and g + 8192): every ordered pair of kinds follows one another
+    assert {(kind(g), kind(g + GRID_MAX)) for g in range(GRID_MAX)} == {(i, j) for i in range(8) for j in range(8)}
+
+    adepths = [kinds[k][1] for k in which]
+    status = [kinds[k][2] for k in which]
+    hdrs = [hdr8[k] for k in which]
+    held = guarded_batch(torch, payloads, dev, [(5 * i + 1) % 16 for i in range(8)], fill=0xEE)
+    pick = torch.from_numpy(which).to(dev)
+    src = lzo.DeviceBatch(held.arena, held.off[pick].contiguous(), held.length[pick].contiguous())
+    many = [payloads[k] for k in which]
+    for with_hdr, masks in ((True, True), (False, False)):
+        one = C.expect(payloads, [k[1] for k in kinds], hdr8 if with_hdr else None, C.CK_ITBID, [k[2] for k in kinds])
+        want = tuple(w[which] for w in one)                             # the oracle ran once per distinct payload
+        got = check_dev_once(dev, many, adepths, hdrs if with_hdr else None, C.CK_ITBID, masks=masks, status=status,
+                             src=src)
+        same(got, want)
+    assert one[0].tolist() == [0, 0, 0, 0, C.E_TRUNCATED, C.EINVAL, -6, 0]
+    f = [C.report_fields(r) for r in one[1]]
+    assert f[0]["count"][C.S_LOOP] == 1024 and f[1]["live"] == f[1]["used_home"] == 0 and not one[1][1].any()
+    assert f[4]["live"] == len(t.hashes) and f[3]["count"][C.S_ISLAND] == 1
+    C.assert_directed(fan, got[0][7], got[1][7])
 
 
 # ---------------------------------------------------------------------------
@@ -319,3 +428,19 @@ def test_batch_failed_chunk(chunky, debug_env):
     same((err[kept], rep[kept], sm[kept], im[kept]), tuple(w[kept] for w in want))
     debug_env("chunk_mb=1")
     same(as_tuple(check.check_batch(stored, C.CK_ITBID, masks=True)), want)
+
+
+def test_batch_directed(oracle):
+    """The count and walk tables at adepth 1, 6 and 10 as records, LZO and
+    stored alternately, through the decode and the chunk pipeline: results in
+    caller order, equal to the oracle's and to the closed forms."""
+    tables = C.directed("counts", (1, 6, 10)) + C.directed("walk", (1, 6, 10))
+    assert len(tables) == 8 + 30
+    stored = [t.rec if b % 2 else C.lzo_record(oracle, t.rec) for b, t in enumerate(tables)]
+    want = expect_batch(stored, [C.payload_of(t.rec) for t in tables], C.CK_ITBID)
+    res = check.check_batch(stored, C.CK_ITBID, masks=True)
+    same(as_tuple(res), want)
+    assert res.len_ok.tolist() == [1] * len(tables)
+    got = as_tuple(res)
+    for b, t in enumerate(tables):
+        C.assert_directed(t, got[0][b], got[1][b], got[2][b], got[3][b])
