@@ -33,15 +33,15 @@ int pom_itb_check_dev(const uint8_t *payload, const uint64_t *payload_off,
                                        slot_mask, ite_mask, err, (hipStream_t)stream);
 }
 
-/* What the check needs of a record's struct itbh; w: its block. */
-static void header_facts(const uint8_t *rec, const struct pom_walk_block *w, struct pom_check_hdr *h)
+/* What the check needs of a record's struct itbh. */
+void pom_check_header_facts(const uint8_t *rec, int is_lzo, struct pom_check_hdr *h)
 {
     uint32_t len;
     memset(h, 0, sizeof *h);
     memcpy(&h->entries, rec + POM_ITBH_ENTRIES_OFF, 4);
     memcpy(&h->max_offset, rec + POM_ITBH_MAX_OFFSET_OFF, 4);
     memcpy(&h->pseudo_conflicts, rec + POM_ITBH_PSEUDO_CONFLICTS_OFF, 4);
-    memcpy(&len, rec + (w->is_lzo ? POM_ITBH_ZLEN_OFF : POM_ITBH_LEN_OFF), 4);
+    memcpy(&len, rec + (is_lzo ? POM_ITBH_ZLEN_OFF : POM_ITBH_LEN_OFF), 4);
     h->ulen = len;
     memcpy(&h->inf, rec + POM_ITBH_INF_OFF, 2);
     memcpy(&h->itu, rec + POM_ITBH_ITU_OFF, 2);
@@ -91,7 +91,7 @@ int pom_itb_check_batch(const uint8_t *const *rec, const size_t *rec_len, size_t
             status[m] = 0;
             kerr[m] = LZO_E_ERROR;                                  /* until its chunk delivers */
             out_len[m] = 0;
-            header_facts(rec[b], &w, &hdr[m]);
+            pom_check_header_facts(rec[b], w.is_lzo, &hdr[m]);
             m++;
         }
         struct pom_check_sink G = {.is_lzo = is_lzo, .cap = cap, .adepth = adepth, .hdr = hdr, .idx = idx,

@@ -283,3 +283,64 @@ void pom_layout_check(struct layout *L, const size_t *ids, size_t nb, size_t nlz
     K->o_res = take(&o, POM_ALIGN_UP(K->res_bytes, 256));
     L->dtotal = o;
 }
+
+size_t pom_split_stream_room(size_t n)
+{
+    return POM_ALIGN_UP(n + n / 16 + 64 + 3, 16);
+}
+
+void pom_layout_split(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, size_t scratch, size_t split_scratch, size_t enc_scratch)
+{
+    size_t in, out, o = 0, r = 0, news = 0, streams = 0;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct itb_split_layout *K = &L->u.split;
+    for (size_t i = 0; i < nb; i++) {
+        const size_t dl = i < nlzo ? cap[ids[i]] : src_len[ids[i]];
+        news += POM_ALIGN_UP(dl, 16);
+        streams += 2 * pom_split_stream_room(dl);
+    }
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    K->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_newoff = take(&o, 8 * nb);
+    K->o_esrcoff = take(&o, 16 * nb);
+    K->o_edstoff = take(&o, 16 * nb);
+    K->o_pfrom = take(&o, 16 * nb);
+    K->o_pto = take(&o, 16 * nb);
+    K->o_hdr = take(&o, 32 * nb);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    L->o_status = take(&o, 4 * nb);
+    L->o_outlen = take(&o, 4 * nb);
+    K->o_newcap = take(&o, 4 * nb);
+    K->o_edstcap = take(&o, 8 * nb);
+    K->o_plen = take(&o, 8 * nb);
+    K->scan.o_adepth = take(&o, nb);
+    K->o_sd = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    L->o_dst = o;
+    K->r_status = take(&r, 4 * nb);
+    K->r_outlen = take(&r, 4 * nb);
+    r = POM_ALIGN_UP(r, 8);
+    K->r_result = take(&r, 48 * nb);
+    K->r_elen = take(&r, 8 * nb);
+    K->r_est = take(&r, 8 * nb);
+    K->res_bytes = r;
+    K->pcap = 2 * news;
+    K->o_hres = o;
+    K->o_hrec = POM_ALIGN_UP(o + r, 256);
+    L->htotal = K->o_hrec + K->pcap;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_new = take(&o, POM_ALIGN_UP(news, 256));
+    K->o_sscr = take(&o, POM_ALIGN_UP(split_scratch, 256));
+    K->o_esrclen = take(&o, POM_ALIGN_UP(8 * nb, 256));
+    K->escr_bytes = enc_scratch;
+    K->o_escr = take(&o, POM_ALIGN_UP(enc_scratch, 256));
+    K->o_z = take(&o, POM_ALIGN_UP(streams, 256));
+    K->o_res = take(&o, POM_ALIGN_UP(r, 256));
+    K->o_pack = take(&o, POM_ALIGN_UP(K->pcap, 256));
+    L->dtotal = o;
+}

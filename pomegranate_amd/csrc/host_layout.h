@@ -154,6 +154,39 @@ struct itb_check_layout {
     int masks;
 };
 
+/* The ITB split: the check's partition and inputs, and what a writer adds.
+ * dl(i), block i's decoded length, is its capacity (LZO) or its staged length
+ * (stored); a stored block is split where it is staged.  Among the inputs, so
+ * that one H2D brings them up: the split depths, each new payload's place and
+ * capacity (dl), and for the encoder's 2 * nb blocks -- half 0 the old
+ * payloads, half 1 the new ones -- their sources, stream slots and slot sizes;
+ * the three pack arrays are filled and uploaded once the results are back.
+ * Device only: the new payloads, the split's scratch, the encoder's lengths
+ * (gathered from the results on the device) and scratch, the stream slots,
+ * the packed output.  The results -- the decoders' two words, the 48-byte
+ * results, the encoder's out_len and status -- lie alike on both sides and
+ * come back in one copy; what each half is stored as is decided from them, and
+ * exactly those bytes follow in a second one. */
+struct itb_split_layout {
+    struct scan_layout scan;
+    size_t o_hdr, o_sd;             /* struct pom_check_hdr, u8 per block */
+    size_t o_newoff, o_newcap;      /* u64, u32 per block: from the device staging's start */
+    size_t o_esrcoff, o_edstoff;    /* u64, 2 * nb */
+    size_t o_edstcap;               /* u32, 2 * nb */
+    size_t o_pfrom, o_pto, o_plen;  /* u64, u64, u32, 2 * nb: the pack of what is delivered */
+    size_t o_new, o_sscr;           /* device only */
+    size_t o_esrclen;               /* device only: u32, 2 * nb */
+    size_t o_escr, escr_bytes;
+    size_t o_z;                     /* device only: the stream slots */
+    size_t o_res, o_hres;
+    size_t r_status, r_outlen;      /* i32, u32 per block: adjacent, in this order */
+    size_t r_result;                /* 48 bytes per block, 8-byte aligned */
+    size_t r_elen, r_est;           /* u32, i32, 2 * nb */
+    size_t res_bytes;
+    size_t pcap;                    /* room for the delivered halves */
+    size_t o_pack, o_hrec;          /* device, host */
+};
+
 struct layout {
     size_t nb;
     const size_t *ids;
@@ -174,6 +207,7 @@ struct layout {
         struct col_layout col;
         struct req_layout req;
         struct itb_check_layout check;
+        struct itb_split_layout split;
     } u;
 };
 
@@ -200,6 +234,13 @@ void pom_layout_req(struct layout *L, const size_t *ids, size_t nb, size_t nlzo,
 /* masks != 0: the results have room for the slot and ITE masks */
 void pom_layout_check(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
                       const size_t *cap, int masks, size_t scratch);
+
+/* split_scratch, enc_scratch: what the split of nb blocks and the encoder of
+ * 2 * nb blocks need. */
+void pom_layout_split(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, size_t scratch, size_t split_scratch, size_t enc_scratch);
+/* The room an LZO1X-1 stream of n bytes can take, rounded up to 16. */
+size_t pom_split_stream_room(size_t n);
 
 /* The staging of a group of k single calls (host_single.c).  The header
  * arrays, then the inputs, lie alike on both sides and go up in one H2D copy

@@ -10,9 +10,11 @@
  * read (col_slice.hip), the lookup (itb_find.hip) and the key/value get
  * (itb_kvget.hip) carry requests, the last two as one operation told apart by
  * a descriptor (struct req_spec) and their kernels; the ITB check
- * (itb_check.hip) has the walks' partition and fixed-size results.  Their
+ * (itb_check.hip) has the walks' partition and fixed-size results; the ITB
+ * split (itb_split.hip) has the check's partition, writes, and runs the encoder
+ * over both halves behind it.  Their
  * callers (gc_scan.c, gc_stat.c, readdir.c, kvlist.c, column_codec.c, lookup.c,
- * kvget.c, check.c) select the blocks and put the results in the caller's order.
+ * kvget.c, check.c, itbsplit.c) select the blocks and put the results in the caller's order.
  */
 #include <pthread.h>
 #include <stdlib.h>
@@ -25,9 +27,11 @@
 #include "pom_check.h"
 #include "pom_column.h"
 #include "pom_gc.h"
+#include "pom_itb.h"
 #include "pom_kvget.h"
 #include "pom_kvlist.h"
 #include "pom_lookup.h"
+#include "pom_split.h"
 
 /* Per block of a chunk with stored blocks: where the walk finds the payload
  * (decoded behind o_dst, or stored as staged behind o_src), the decoders'
@@ -901,6 +905,215 @@ int pom_itb_check_chunked(const uint8_t *const *src, const size_t *src_len, size
                           struct pom_check_sink *sink)
 {
     struct hbatch B = {.ops = &ck_ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
+                       .sink = sink};
+    return pom_host_batch(&B, nblocks);
+}
+
+/* ------------------------------------------------------------------------ */
+/* The ITB split: decode, check and split (itb_split.hip), encode both halves */
+/* ------------------------------------------------------------------------ */
+/* The check's partition (LZO records decoded, stored ones split where they
+ * are staged), and the first operation that writes.  Kernels on the chunk's
+ * stream: the decoders; pom_itb_split_dev, which rewrites each old payload's
+ * bitmap and index in place and writes the new payloads beside them; the
+ * gather of the encoder's 2 * nb source lengths from the results;
+ * lzo_mi355x_compress_dev over the 2 * nb halves where they lie.  The results
+ * (the decoders' words, the 48-byte results, the encoder's out_len and status)
+ * come back in one copy queued behind the kernels.  Once they are back the
+ * host applies itb_lzo_compress's not-smaller rule to each half, and the pack
+ * kernel gathers exactly what is delivered -- the stream, or the payload of a
+ * half that did not compress -- for the second D2H.  Staging:
+ * pom_layout_split (host_layout.h).  No decoded byte leaves the device unless
+ * a half does not compress. */
+static size_t sp_cap(const struct hbatch *B, size_t b)
+{
+    const struct pom_split_sink *C = B->sink;
+    return C->cap[b];
+}
+
+static size_t sp_dl(const struct hbatch *B, size_t b)
+{
+    const struct pom_split_sink *C = B->sink;
+    return C->is_lzo[b] ? B->cap[b] : B->src_len[b];
+}
+
+/* the chunk budget counts the new payload, the two stream slots, the delivered halves and the small arrays */
+static size_t sp_extra_cost(const struct hbatch *B, size_t b)
+{
+    const struct pom_split_sink *C = B->sink;
+    const size_t dl = C->is_lzo[b] ? C->cap[b] : B->src_len[b];
+    return 3 * dl + 2 * pom_split_stream_room(dl) + 256;
+}
+
+static void sp_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    pom_layout_split(L, ids, nb, nlzo, B->src_len, B->cap, lzo_mi355x_decompress_scratch((uint32_t)nlzo),
+                     pom_itb_split_scratch((uint32_t)nb), lzo_mi355x_compress_scratch((uint32_t)(2 * nb)));
+}
+
+static int sp_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    const struct pom_split_sink *C = B->sink;
+    const struct itb_split_layout *K = &L->u.split;
+    const size_t nb = L->nb;
+    struct pom_check_hdr *hd = (struct pom_check_hdr *)(h + K->o_hdr);
+    uint64_t *no = (uint64_t *)(h + K->o_newoff), *eso = (uint64_t *)(h + K->o_esrcoff);
+    uint64_t *edo = (uint64_t *)(h + K->o_edstoff);
+    uint32_t *nc = (uint32_t *)(h + K->o_newcap), *edc = (uint32_t *)(h + K->o_edstcap);
+    const uint64_t *sco = (const uint64_t *)(h + K->scan.o_scanoff);
+    size_t at = 0, z = 0;
+    if (2 * nb > 0xFFFFFFFFu)
+        return -1;
+    pom_stage_inputs(L, h, B);
+    stage_scan(L, &K->scan, h, C->adepth);
+    memset(h + K->o_pfrom, 0, 16 * nb);
+    memset(h + K->o_pto, 0, 16 * nb);
+    memset(h + K->o_plen, 0, 8 * nb);
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = L->ids[i], dl = sp_dl(B, b);
+        hd[i] = C->hdr[b];
+        h[K->o_sd + i] = C->sd[b];
+        no[i] = K->o_new + at;
+        nc[i] = (uint32_t)dl;
+        at += POM_ALIGN_UP(dl, 16);
+        eso[i] = sco[i];
+        eso[nb + i] = no[i];
+    }
+    for (size_t k = 0; k < 2 * nb; k++) {
+        const size_t room = pom_split_stream_room(sp_dl(B, L->ids[k % nb]));
+        edo[k] = K->o_z + z;
+        edc[k] = (uint32_t)room;
+        z += room;
+    }
+    return 0;
+}
+
+static int sp_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct itb_split_layout *K = &L->u.split;
+    uint8_t *d = S->dmem, *res = d + K->o_res;
+    const uint32_t nb = (uint32_t)L->nb;
+    struct pom_split_result *result = (struct pom_split_result *)(res + K->r_result);
+    (void)B;
+    if (pom_decode_lzo_blocks(S, L, 0) != 0)
+        return -1;
+    if (pom_itb_split_dev(d, (const uint64_t *)(d + K->scan.o_scanoff), (const uint32_t *)(d + L->o_outlen),
+                          (const int32_t *)(d + L->o_status), d + K->scan.o_adepth,
+                          (const struct pom_check_hdr *)(d + K->o_hdr), d + K->o_sd, nb, d,
+                          (const uint64_t *)(d + K->o_newoff), (const uint32_t *)(d + K->o_newcap), result,
+                          d + K->o_sscr, S->stream) != 0)
+        return -1;
+    if (lzo_mi355x_launch_itb_split_lens(result, nb, (uint32_t *)(d + K->o_esrclen), S->stream) != 0)
+        return -1;
+    if (lzo_mi355x_compress_dev(d, (const uint64_t *)(d + K->o_esrcoff), (const uint32_t *)(d + K->o_esrclen), d,
+                                (const uint64_t *)(d + K->o_edstoff), (const uint32_t *)(d + K->o_edstcap),
+                                (uint32_t *)(res + K->r_elen), (int32_t *)(res + K->r_est), 2 * nb, d + K->o_escr,
+                                S->stream) != 0)
+        return -1;
+    /* status, then out_len: adjacent among the inputs and among the results */
+    if (hipMemcpyAsync(res + K->r_status, d + L->o_status, 8 * L->nb, hipMemcpyDeviceToDevice, S->stream) != hipSuccess)
+        return -1;
+    return hipMemcpyAsync(S->hmem + K->o_hres, res, K->res_bytes, hipMemcpyDeviceToHost, S->stream) == hipSuccess
+               ? 0 : -1;
+}
+
+/* Half k (0 ... 2 * nb) of the chunk as it is delivered: the bytes, and whether they are its stream. */
+static size_t sp_half(const struct layout *L, const uint8_t *h, size_t k, int *lzo)
+{
+    const struct itb_split_layout *K = &L->u.split;
+    const uint8_t *res = h + K->o_hres;
+    const size_t i = k % L->nb;
+    struct pom_split_result r;
+    memcpy(&r, res + K->r_result + sizeof r * i, sizeof r);
+    const uint32_t ulen = k < L->nb ? r.old_len : r.new_len;
+    const uint32_t z = ((const uint32_t *)(res + K->r_elen))[k];
+    *lzo = 0;
+    if (r.err != 0 || r.moved == 0 || ulen < POM_ITB_SIZE)
+        return 0;
+    *lzo = z < ulen - (POM_ITB_SIZE - POM_ITB_ITE_OFF);
+    return *lzo ? z : ulen - (POM_ITB_SIZE - POM_ITB_ITE_OFF);
+}
+
+static int sp_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
+{
+    const struct itb_split_layout *K = &L->u.split;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    const size_t nb = L->nb;
+    uint64_t *pf = (uint64_t *)(h + K->o_pfrom), *pt = (uint64_t *)(h + K->o_pto);
+    uint32_t *pl = (uint32_t *)(h + K->o_plen);
+    const uint64_t *eso = (const uint64_t *)(h + K->o_esrcoff), *edo = (const uint64_t *)(h + K->o_edstoff);
+    const int32_t *est = (const int32_t *)(h + K->o_hres + K->r_est);
+    size_t total = 0;
+    (void)B;
+    for (size_t k = 0; k < 2 * nb; k++) {
+        int lzo;
+        const size_t n = sp_half(L, h, k, &lzo);
+        if (n && est[k] != 0)
+            return -1;                              /* (the slots hold any stream: the encoder cannot fail) */
+        pf[k] = lzo ? edo[k] : eso[k];
+        pt[k] = total;
+        pl[k] = (uint32_t)n;
+        total += POM_ALIGN_UP(n, 16);
+    }
+    if (total > K->pcap)
+        return -1;
+    if (total &&
+        (hipMemcpyAsync(d + K->o_pfrom, pf, 32 * nb, hipMemcpyHostToDevice, S->stream) != hipSuccess ||
+         hipMemcpyAsync(d + K->o_plen, pl, 8 * nb, hipMemcpyHostToDevice, S->stream) != hipSuccess ||
+         lzo_mi355x_launch_pack(d, (const uint64_t *)(d + K->o_pfrom), (const uint32_t *)(d + K->o_plen),
+                                (const uint32_t *)(d + K->o_plen), (const uint64_t *)(d + K->o_pto), d + K->o_pack,
+                                (uint32_t)(2 * nb), S->stream) != 0 ||
+         hipMemcpyAsync(h + K->o_hrec, d + K->o_pack, total, hipMemcpyDeviceToHost, S->stream) != hipSuccess))
+        return -1;
+    *packed = total;
+    return 0;
+}
+
+static int sp_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct pom_split_sink *C = B->sink;
+    const struct itb_split_layout *K = &L->u.split;
+    const uint8_t *h = S->hmem, *res = h + K->o_hres;
+    const size_t nb = L->nb;
+    const int32_t *st = (const int32_t *)(res + K->r_status);
+    const uint32_t *ol = (const uint32_t *)(res + K->r_outlen);
+    const uint64_t *pt = (const uint64_t *)(h + K->o_pto);
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = L->ids[i], to = C->idx[b];
+        struct pom_split_result *r = &C->result[to];
+        int lzo_o, lzo_n;
+        const size_t no = sp_half(L, h, i, &lzo_o), nn = sp_half(L, h, nb + i, &lzo_n);
+        C->status[b] = st[i];
+        C->out_len[b] = ol[i];
+        C->delivered[b] = 1;
+        memcpy(r, res + K->r_result + sizeof *r * i, sizeof *r);
+        C->err[to] = r->err;
+        C->old_len[to] = C->new_len[to] = 0;
+        if (r->err != 0 || r->moved == 0)
+            continue;
+        if (POM_ITBH_SIZE + no > C->out_cap[to] || POM_ITBH_SIZE + nn > C->out_cap[to]) {
+            C->err[to] = LZO_E_OUTPUT_OVERRUN;
+            continue;
+        }
+        if (pom_itb_split_headers(C->rec_hdr[b], C->sd[b], r, lzo_o ? (uint32_t)no : POM_SPLIT_NO_STREAM,
+                                  lzo_n ? (uint32_t)nn : POM_SPLIT_NO_STREAM, C->old_out[to], C->new_out[to]) < 0)
+            return -1;
+        memcpy(C->old_out[to] + POM_ITBH_SIZE, h + K->o_hrec + pt[i], no);
+        memcpy(C->new_out[to] + POM_ITBH_SIZE, h + K->o_hrec + pt[nb + i], nn);
+        C->old_len[to] = POM_ITBH_SIZE + no;
+        C->new_len[to] = POM_ITBH_SIZE + nn;
+    }
+    return 0;
+}
+
+/* (an undelivered ITB: the caller sees it in `delivered`) */
+static const struct chunk_ops sp_ops = {"itb split", 0, sp_cap, sp_extra_cost, NULL, sp_layout,
+                                        sp_stage, sp_kernels, sp_collect, sp_unpack};
+
+int pom_itb_split_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                          struct pom_split_sink *sink)
+{
+    struct hbatch B = {.ops = &sp_ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
                        .sink = sink};
     return pom_host_batch(&B, nblocks);
 }

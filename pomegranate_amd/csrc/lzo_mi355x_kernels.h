@@ -344,6 +344,54 @@ int lzo_mi355x_launch_itb_check(const uint8_t *payload, const uint64_t *payload_
                                 uint32_t flags, struct pom_check_report *report, uint64_t *slot_mask,
                                 uint64_t *ite_mask, int32_t *err, hipStream_t stream);
 
+/* The ITB split (itb_split.hip): the second launch of pom_itb_split_dev of
+ * include/pom_split.h, behind the check's, whose reports and err it reads.
+ * payload and new_payload are 16-byte aligned; the caller has seen to hdr. */
+struct pom_split_result;
+int lzo_mi355x_launch_itb_split(uint8_t *payload, const uint64_t *payload_off, const uint8_t *adepth,
+                                const struct pom_check_hdr *hdr, const uint8_t *split_depth, uint32_t nitb,
+                                uint8_t *new_payload, const uint64_t *new_off, const uint32_t *new_cap,
+                                const struct pom_check_report *ck_report, const int32_t *ck_err,
+                                struct pom_split_result *result, hipStream_t stream);
+
+/* The encoder's source lengths of 2 * nitb halves from the results on the
+ * device: len[b] = old_len - 264, len[nitb + b] = new_len - 264, 0 where
+ * nothing is produced. */
+int lzo_mi355x_launch_itb_split_lens(const struct pom_split_result *result, uint32_t nitb, uint32_t *len,
+                                     hipStream_t stream);
+
+/* Host side (host_records.c), not part of the ABI: the check's pipeline with
+ * the split and the encoder of both halves behind each chunk's decode.  Block
+ * k of the call is the caller's record idx[k], whose header is rec_hdr[k] (264
+ * bytes).  A delivered block gets status[k], out_len[k], its result at
+ * result[idx[k]], err[idx[k]] (the result's err, or LZO_E_OUTPUT_OVERRUN when a
+ * half does not fit out_cap), and, when something is produced and fits, both
+ * stored records in old_out / new_out with their lengths.  A block whose chunk
+ * is not delivered keeps what the caller put there.  Up go the payloads, 32
+ * bytes of header facts and the split depth; back come the results and the two
+ * stored payloads. */
+struct pom_split_sink {
+    const uint8_t *is_lzo;
+    const size_t *cap;
+    const uint8_t *adepth;
+    const struct pom_check_hdr *hdr;    /* per block */
+    const uint8_t *sd;                  /* per block: the split depth in effect */
+    const uint8_t *const *rec_hdr;      /* per block */
+    const size_t *idx;
+    int32_t *status;
+    uint32_t *out_len;
+    uint8_t *delivered;                 /* per block: 1 once its chunk is delivered */
+    uint8_t *const *old_out, *const *new_out;   /* the caller's, in the caller's order */
+    const size_t *out_cap;
+    size_t *old_len, *new_len;
+    struct pom_split_result *result;
+    int *err;
+};
+int pom_itb_split_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                          struct pom_split_sink *sink);
+/* What the check needs of a record's struct itbh (check.c); is_lzo: the record is COMPR_LZO. */
+void pom_check_header_facts(const uint8_t *rec, int is_lzo, struct pom_check_hdr *h);
+
 /* Host side (host_records.c), not part of the ABI: pom_gc_scan_chunked's
  * pipeline (LZO records decoded, stored ones checked as staged) with the check
  * behind each chunk's decode.  Block k of the call is the caller's record

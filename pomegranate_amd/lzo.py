@@ -73,6 +73,8 @@ EXPORTS = (
     "pom_kvget_dev", "pom_kvget_batch",
     # include/pom_check.h
     "pom_itb_check_dev", "pom_itb_check_batch",
+    # include/pom_split.h
+    "pom_itb_split_dev", "pom_itb_split_scratch", "pom_itb_split_headers", "pom_itb_split_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
