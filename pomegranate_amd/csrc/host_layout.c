@@ -344,3 +344,55 @@ void pom_layout_split(struct layout *L, const size_t *ids, size_t nb, size_t nlz
     K->o_pack = take(&o, POM_ALIGN_UP(K->pcap, 256));
     L->dtotal = o;
 }
+
+void pom_layout_sweep(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, size_t scratch, size_t sweep_scratch, size_t enc_scratch)
+{
+    size_t in, out, o = 0, r = 0, payloads = 0, streams = 0;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct itb_sweep_layout *K = &L->u.sweep;
+    for (size_t i = 0; i < nb; i++) {
+        const size_t dl = i < nlzo ? cap[ids[i]] : src_len[ids[i]];
+        payloads += POM_ALIGN_UP(dl, 16);
+        streams += pom_split_stream_room(dl);
+    }
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    K->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_edstoff = take(&o, 8 * nb);
+    K->o_pfrom = take(&o, 8 * nb);
+    K->o_pto = take(&o, 8 * nb);
+    K->o_hdr = take(&o, 32 * nb);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    L->o_status = take(&o, 4 * nb);
+    L->o_outlen = take(&o, 4 * nb);
+    K->o_budget = take(&o, 4 * nb);
+    K->o_edstcap = take(&o, 4 * nb);
+    K->o_plen = take(&o, 4 * nb);
+    K->scan.o_adepth = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    L->o_dst = o;
+    K->r_status = take(&r, 4 * nb);
+    K->r_outlen = take(&r, 4 * nb);
+    r = POM_ALIGN_UP(r, 8);
+    K->r_result = take(&r, 32 * nb);
+    K->r_elen = take(&r, 4 * nb);
+    K->r_est = take(&r, 4 * nb);
+    K->res_bytes = r;
+    K->pcap = payloads;
+    K->o_hres = o;
+    K->o_hrec = POM_ALIGN_UP(o + r, 256);
+    L->htotal = K->o_hrec + K->pcap;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_sscr = take(&o, POM_ALIGN_UP(sweep_scratch, 256));
+    K->o_esrclen = take(&o, POM_ALIGN_UP(4 * nb, 256));
+    K->escr_bytes = enc_scratch;
+    K->o_escr = take(&o, POM_ALIGN_UP(enc_scratch, 256));
+    K->o_z = take(&o, POM_ALIGN_UP(streams, 256));
+    K->o_res = take(&o, POM_ALIGN_UP(r, 256));
+    K->o_pack = take(&o, POM_ALIGN_UP(K->pcap, 256));
+    L->dtotal = o;
+}

@@ -187,6 +187,35 @@ struct itb_split_layout {
     size_t o_pack, o_hrec;          /* device, host */
 };
 
+/* The ITB sweep: the split's staging without a second half.  A payload is
+ * swept where it was decoded (or staged) and encoded from there, so the
+ * encoder's sources are the scan offsets; among the inputs, beside the
+ * check's: the budgets, each stream slot and its size; the three pack arrays
+ * are filled and uploaded once the results are back.  Device only: the
+ * sweep's scratch, the encoder's lengths (gathered from the results on the
+ * device) and scratch, the stream slots, the packed output.  The results --
+ * the decoders' two words, the 32-byte results, the encoder's out_len and
+ * status -- lie alike on both sides and come back in one copy; what each
+ * record is stored as is decided from them, and exactly those bytes follow in
+ * a second one. */
+struct itb_sweep_layout {
+    struct scan_layout scan;
+    size_t o_hdr, o_budget;         /* struct pom_check_hdr, u32 per block */
+    size_t o_edstoff, o_edstcap;    /* u64, u32 per block */
+    size_t o_pfrom, o_pto, o_plen;  /* u64, u64, u32 per block: the pack of what is delivered */
+    size_t o_sscr;                  /* device only */
+    size_t o_esrclen;               /* device only: u32 per block */
+    size_t o_escr, escr_bytes;
+    size_t o_z;                     /* device only: the stream slots */
+    size_t o_res, o_hres;
+    size_t r_status, r_outlen;      /* i32, u32 per block: adjacent, in this order */
+    size_t r_result;                /* 32 bytes per block, 8-byte aligned */
+    size_t r_elen, r_est;           /* u32, i32 per block */
+    size_t res_bytes;
+    size_t pcap;                    /* room for the delivered payloads */
+    size_t o_pack, o_hrec;          /* device, host */
+};
+
 struct layout {
     size_t nb;
     const size_t *ids;
@@ -208,6 +237,7 @@ struct layout {
         struct req_layout req;
         struct itb_check_layout check;
         struct itb_split_layout split;
+        struct itb_sweep_layout sweep;
     } u;
 };
 
@@ -241,6 +271,10 @@ void pom_layout_split(struct layout *L, const size_t *ids, size_t nb, size_t nlz
                       const size_t *cap, size_t scratch, size_t split_scratch, size_t enc_scratch);
 /* The room an LZO1X-1 stream of n bytes can take, rounded up to 16. */
 size_t pom_split_stream_room(size_t n);
+
+/* sweep_scratch, enc_scratch: what the sweep and the encoder of nb blocks need. */
+void pom_layout_sweep(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                      const size_t *cap, size_t scratch, size_t sweep_scratch, size_t enc_scratch);
 
 /* The staging of a group of k single calls (host_single.c).  The header
  * arrays, then the inputs, lie alike on both sides and go up in one H2D copy

@@ -12,9 +12,10 @@
  * a descriptor (struct req_spec) and their kernels; the ITB check
  * (itb_check.hip) has the walks' partition and fixed-size results; the ITB
  * split (itb_split.hip) has the check's partition, writes, and runs the encoder
- * over both halves behind it.  Their
+ * over both halves behind it; the ITB sweep (itb_sweep.hip) is the split with
+ * one payload and no second half.  Their
  * callers (gc_scan.c, gc_stat.c, readdir.c, kvlist.c, column_codec.c, lookup.c,
- * kvget.c, check.c, itbsplit.c) select the blocks and put the results in the caller's order.
+ * kvget.c, check.c, itbsplit.c, itbsweep.c) select the blocks and put the results in the caller's order.
  */
 #include <pthread.h>
 #include <stdlib.h>
@@ -32,6 +33,7 @@
 #include "pom_kvlist.h"
 #include "pom_lookup.h"
 #include "pom_split.h"
+#include "pom_sweep.h"
 
 /* Per block of a chunk with stored blocks: where the walk finds the payload
  * (decoded behind o_dst, or stored as staged behind o_src), the decoders'
@@ -1114,6 +1116,197 @@ int pom_itb_split_chunked(const uint8_t *const *src, const size_t *src_len, size
                           struct pom_split_sink *sink)
 {
     struct hbatch B = {.ops = &sp_ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
+                       .sink = sink};
+    return pom_host_batch(&B, nblocks);
+}
+
+/* ------------------------------------------------------------------------ */
+/* The ITB sweep: decode, check and sweep (itb_sweep.hip), encode           */
+/* ------------------------------------------------------------------------ */
+/* The split's partition and order with one payload a block.  Kernels on the
+ * chunk's stream: the decoders; pom_itb_sweep_dev, which rewrites each
+ * payload's bitmap and index in place; the gather of the encoder's nb source
+ * lengths from the results; lzo_mi355x_compress_dev over the payloads where
+ * they lie.  The results (the decoders' words, the 32-byte results, the
+ * encoder's out_len and status) come back in one copy queued behind the
+ * kernels.  Once they are back the host applies itb_lzo_compress's
+ * not-smaller rule, and the pack kernel gathers exactly what is delivered --
+ * the stream, or the payload when it did not compress -- for the second D2H.
+ * A block nothing was removed from delivers nothing: its stored record is
+ * still right.  Staging: pom_layout_sweep (host_layout.h). */
+static size_t sw_cap(const struct hbatch *B, size_t b)
+{
+    const struct pom_sweep_sink *C = B->sink;
+    return C->cap[b];
+}
+
+static size_t sw_dl(const struct hbatch *B, size_t b)
+{
+    const struct pom_sweep_sink *C = B->sink;
+    return C->is_lzo[b] ? B->cap[b] : B->src_len[b];
+}
+
+/* the chunk budget counts the stream slot, the delivered payload (device and host) and the small arrays */
+static size_t sw_extra_cost(const struct hbatch *B, size_t b)
+{
+    const struct pom_sweep_sink *C = B->sink;
+    const size_t dl = C->is_lzo[b] ? C->cap[b] : B->src_len[b];
+    return 2 * dl + pom_split_stream_room(dl) + 256;
+}
+
+static void sw_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    pom_layout_sweep(L, ids, nb, nlzo, B->src_len, B->cap, lzo_mi355x_decompress_scratch((uint32_t)nlzo),
+                     pom_itb_sweep_scratch((uint32_t)nb), lzo_mi355x_compress_scratch((uint32_t)nb));
+}
+
+static int sw_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    const struct pom_sweep_sink *C = B->sink;
+    const struct itb_sweep_layout *K = &L->u.sweep;
+    const size_t nb = L->nb;
+    struct pom_check_hdr *hd = (struct pom_check_hdr *)(h + K->o_hdr);
+    uint64_t *edo = (uint64_t *)(h + K->o_edstoff);
+    uint32_t *edc = (uint32_t *)(h + K->o_edstcap), *bud = (uint32_t *)(h + K->o_budget);
+    size_t z = 0;
+    if (nb > 0xFFFFFFFFu)
+        return -1;
+    pom_stage_inputs(L, h, B);
+    stage_scan(L, &K->scan, h, C->adepth);
+    memset(h + K->o_pfrom, 0, 8 * nb);
+    memset(h + K->o_pto, 0, 8 * nb);
+    memset(h + K->o_plen, 0, 4 * nb);
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = L->ids[i], room = pom_split_stream_room(sw_dl(B, b));
+        hd[i] = C->hdr[b];
+        bud[i] = C->budget[b];
+        edo[i] = K->o_z + z;
+        edc[i] = (uint32_t)room;
+        z += room;
+    }
+    return 0;
+}
+
+static int sw_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct itb_sweep_layout *K = &L->u.sweep;
+    uint8_t *d = S->dmem, *res = d + K->o_res;
+    const uint32_t nb = (uint32_t)L->nb;
+    struct pom_sweep_result *result = (struct pom_sweep_result *)(res + K->r_result);
+    (void)B;
+    if (pom_decode_lzo_blocks(S, L, 0) != 0)
+        return -1;
+    if (pom_itb_sweep_dev(d, (const uint64_t *)(d + K->scan.o_scanoff), (const uint32_t *)(d + L->o_outlen),
+                          (const int32_t *)(d + L->o_status), d + K->scan.o_adepth,
+                          (const struct pom_check_hdr *)(d + K->o_hdr), (const uint32_t *)(d + K->o_budget), nb, result,
+                          d + K->o_sscr, S->stream) != 0)
+        return -1;
+    if (lzo_mi355x_launch_itb_sweep_lens(result, nb, (uint32_t *)(d + K->o_esrclen), S->stream) != 0)
+        return -1;
+    if (lzo_mi355x_compress_dev(d, (const uint64_t *)(d + K->scan.o_scanoff), (const uint32_t *)(d + K->o_esrclen), d,
+                                (const uint64_t *)(d + K->o_edstoff), (const uint32_t *)(d + K->o_edstcap),
+                                (uint32_t *)(res + K->r_elen), (int32_t *)(res + K->r_est), nb, d + K->o_escr,
+                                S->stream) != 0)
+        return -1;
+    /* status, then out_len: adjacent among the inputs and among the results */
+    if (hipMemcpyAsync(res + K->r_status, d + L->o_status, 8 * L->nb, hipMemcpyDeviceToDevice, S->stream) != hipSuccess)
+        return -1;
+    return hipMemcpyAsync(S->hmem + K->o_hres, res, K->res_bytes, hipMemcpyDeviceToHost, S->stream) == hipSuccess
+               ? 0 : -1;
+}
+
+/* Block i of the chunk as it is delivered: the bytes, and whether they are its stream. */
+static size_t sw_payload(const struct layout *L, const uint8_t *h, size_t i, int *lzo)
+{
+    const struct itb_sweep_layout *K = &L->u.sweep;
+    const uint8_t *res = h + K->o_hres;
+    struct pom_sweep_result r;
+    memcpy(&r, res + K->r_result + sizeof r * i, sizeof r);
+    const uint32_t z = ((const uint32_t *)(res + K->r_elen))[i];
+    *lzo = 0;
+    if (r.err != 0 || r.removed == 0 || r.len < POM_ITB_SIZE)
+        return 0;
+    *lzo = z < r.len - (POM_ITB_SIZE - POM_ITB_ITE_OFF);
+    return *lzo ? z : r.len - (POM_ITB_SIZE - POM_ITB_ITE_OFF);
+}
+
+static int sw_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
+{
+    const struct itb_sweep_layout *K = &L->u.sweep;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    const size_t nb = L->nb;
+    uint64_t *pf = (uint64_t *)(h + K->o_pfrom), *pt = (uint64_t *)(h + K->o_pto);
+    uint32_t *pl = (uint32_t *)(h + K->o_plen);
+    const uint64_t *eso = (const uint64_t *)(h + K->scan.o_scanoff), *edo = (const uint64_t *)(h + K->o_edstoff);
+    const int32_t *est = (const int32_t *)(h + K->o_hres + K->r_est);
+    size_t total = 0;
+    (void)B;
+    for (size_t i = 0; i < nb; i++) {
+        int lzo;
+        const size_t n = sw_payload(L, h, i, &lzo);
+        if (n && est[i] != 0)
+            return -1;                              /* (the slots hold any stream: the encoder cannot fail) */
+        pf[i] = lzo ? edo[i] : eso[i];
+        pt[i] = total;
+        pl[i] = (uint32_t)n;
+        total += POM_ALIGN_UP(n, 16);
+    }
+    if (total > K->pcap)
+        return -1;
+    if (total &&
+        (hipMemcpyAsync(d + K->o_pfrom, pf, 16 * nb, hipMemcpyHostToDevice, S->stream) != hipSuccess ||
+         hipMemcpyAsync(d + K->o_plen, pl, 4 * nb, hipMemcpyHostToDevice, S->stream) != hipSuccess ||
+         lzo_mi355x_launch_pack(d, (const uint64_t *)(d + K->o_pfrom), (const uint32_t *)(d + K->o_plen),
+                                (const uint32_t *)(d + K->o_plen), (const uint64_t *)(d + K->o_pto), d + K->o_pack,
+                                (uint32_t)nb, S->stream) != 0 ||
+         hipMemcpyAsync(h + K->o_hrec, d + K->o_pack, total, hipMemcpyDeviceToHost, S->stream) != hipSuccess))
+        return -1;
+    *packed = total;
+    return 0;
+}
+
+static int sw_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct pom_sweep_sink *C = B->sink;
+    const struct itb_sweep_layout *K = &L->u.sweep;
+    const uint8_t *h = S->hmem, *res = h + K->o_hres;
+    const size_t nb = L->nb;
+    const int32_t *st = (const int32_t *)(res + K->r_status);
+    const uint32_t *ol = (const uint32_t *)(res + K->r_outlen);
+    const uint64_t *pt = (const uint64_t *)(h + K->o_pto);
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = L->ids[i], to = C->idx[b];
+        struct pom_sweep_result *r = &C->result[to];
+        int lzo;
+        const size_t n = sw_payload(L, h, i, &lzo);
+        C->status[b] = st[i];
+        C->out_len[b] = ol[i];
+        C->delivered[b] = 1;
+        memcpy(r, res + K->r_result + sizeof *r * i, sizeof *r);
+        C->err[to] = r->err;
+        C->rec_len[to] = 0;
+        if (r->err != 0 || r->removed == 0)
+            continue;
+        if (POM_ITBH_SIZE + n > C->out_cap[to]) {
+            C->err[to] = LZO_E_OUTPUT_OVERRUN;
+            continue;
+        }
+        if (pom_itb_sweep_header(C->rec_hdr[b], r, lzo ? (uint32_t)n : POM_SPLIT_NO_STREAM, C->out[to]) < 0)
+            return -1;
+        memcpy(C->out[to] + POM_ITBH_SIZE, h + K->o_hrec + pt[i], n);
+        C->rec_len[to] = POM_ITBH_SIZE + n;
+    }
+    return 0;
+}
+
+/* (an undelivered ITB: the caller sees it in `delivered`) */
+static const struct chunk_ops sw_ops = {"itb sweep", 0, sw_cap, sw_extra_cost, NULL, sw_layout,
+                                        sw_stage, sw_kernels, sw_collect, sw_unpack};
+
+int pom_itb_sweep_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                          struct pom_sweep_sink *sink)
+{
+    struct hbatch B = {.ops = &sw_ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
                        .sink = sink};
     return pom_host_batch(&B, nblocks);
 }

@@ -56,8 +56,9 @@ static void put16(uint8_t *h, size_t off, uint16_t v)
 }
 
 /* itb_lzo_compress's rule (mds/itb.c:2904-2945) on one header: the stream is
- * kept when it is smaller than the payload.  Returns whether it is. */
-static int stored_as(uint8_t *h, uint32_t ulen, uint32_t z)
+ * kept when it is smaller than the payload.  Returns whether it is.  (The
+ * sweep's header builder, itbsweep.c, calls it too.) */
+int pom_itb_stored_as(uint8_t *h, uint32_t ulen, uint32_t z)
 {
     const int lzo = z < ulen - POM_ITBH_SIZE;
     put32(h, POM_ITBH_LEN_OFF, lzo ? POM_ITBH_SIZE + z : ulen);
@@ -80,7 +81,7 @@ int pom_itb_split_headers(const uint8_t *old_hdr, uint8_t sd, const struct pom_s
     put32(o, POM_ITBH_MAX_OFFSET_OFF, (uint32_t)r->old_max_offset);
     put32(o, POM_ITBH_PSEUDO_CONFLICTS_OFF, (uint32_t)r->old_pseudo);
     put16(o, POM_ITBH_ITU_OFF, r->old_itu);
-    const int old_lzo = stored_as(o, r->old_len, old_z);
+    const int old_lzo = pom_itb_stored_as(o, r->old_len, old_z);
 
     memcpy(n, o, POM_ITBH_SIZE);
     n[POM_ITBH_FLAG_OFF] = POM_ITB_JUST_SPLIT;
@@ -94,7 +95,7 @@ int pom_itb_split_headers(const uint8_t *old_hdr, uint8_t sd, const struct pom_s
     put32(n, POM_ITBH_PSEUDO_CONFLICTS_OFF, (uint32_t)r->new_pseudo);
     put16(n, POM_ITBH_INF_OFF, r->new_inf);
     put16(n, POM_ITBH_ITU_OFF, r->new_itu);
-    const int new_lzo = stored_as(n, r->new_len, new_z);
+    const int new_lzo = pom_itb_stored_as(n, r->new_len, new_z);
     memset(n + POM_ITBH_TWIN_OFF, 0, 8);
     memset(n + POM_ITBH_SPLIT_RLINK_OFF, 0, 8);
 

@@ -391,6 +391,56 @@ int pom_itb_split_chunked(const uint8_t *const *src, const size_t *src_len, size
                           struct pom_split_sink *sink);
 /* What the check needs of a record's struct itbh (check.c); is_lzo: the record is COMPR_LZO. */
 void pom_check_header_facts(const uint8_t *rec, int is_lzo, struct pom_check_hdr *h);
+/* itb_lzo_compress's not-smaller rule on one 264-byte header (itbsplit.c): a
+ * stream of z bytes is kept when it is smaller than the payload of a record of
+ * ulen bytes; len, zlen and compress_algo are set accordingly.  Returns
+ * whether the stream is kept. */
+int pom_itb_stored_as(uint8_t *h, uint32_t ulen, uint32_t z);
+
+/* The ITB sweep (itb_sweep.hip): the second launch of pom_itb_sweep_dev of
+ * include/pom_sweep.h, behind the check's, whose reports and err it reads.
+ * payload is 16-byte aligned; the caller has seen to hdr.  budget may be
+ * NULL. */
+struct pom_sweep_result;
+int lzo_mi355x_launch_itb_sweep(uint8_t *payload, const uint64_t *payload_off, const uint8_t *adepth,
+                                const struct pom_check_hdr *hdr, const uint32_t *budget, uint32_t nitb,
+                                const struct pom_check_report *ck_report, const int32_t *ck_err,
+                                struct pom_sweep_result *result, hipStream_t stream);
+
+/* The encoder's source lengths of nitb swept payloads from the results on the
+ * device: len[b] = result[b].len - 264, 0 where nothing is produced. */
+int lzo_mi355x_launch_itb_sweep_lens(const struct pom_sweep_result *result, uint32_t nitb, uint32_t *len,
+                                     hipStream_t stream);
+
+/* Host side (host_records.c), not part of the ABI: the split's pipeline with
+ * the sweep and the encoder of the one payload behind each chunk's decode.
+ * Block k of the call is the caller's record idx[k], whose header is
+ * rec_hdr[k] (264 bytes).  A delivered block gets status[k], out_len[k], its
+ * result at result[idx[k]], err[idx[k]] (the result's err, or
+ * LZO_E_OUTPUT_OVERRUN when the record does not fit out_cap), and, when
+ * something was removed and the record fits, the stored record in out with its
+ * length.  A block whose chunk is not delivered keeps what the caller put
+ * there.  Up go the payloads, 32 bytes of header facts and the budget; back
+ * come the results and the one stored payload. */
+struct pom_sweep_sink {
+    const uint8_t *is_lzo;
+    const size_t *cap;
+    const uint8_t *adepth;
+    const struct pom_check_hdr *hdr;    /* per block */
+    const uint32_t *budget;             /* per block: the budget in effect */
+    const uint8_t *const *rec_hdr;      /* per block */
+    const size_t *idx;
+    int32_t *status;
+    uint32_t *out_len;
+    uint8_t *delivered;                 /* per block: 1 once its chunk is delivered */
+    uint8_t *const *out;                /* the caller's, in the caller's order */
+    const size_t *out_cap;
+    size_t *rec_len;
+    struct pom_sweep_result *result;
+    int *err;
+};
+int pom_itb_sweep_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                          struct pom_sweep_sink *sink);
 
 /* Host side (host_records.c), not part of the ABI: pom_gc_scan_chunked's
  * pipeline (LZO records decoded, stored ones checked as staged) with the check

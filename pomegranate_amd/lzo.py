@@ -75,6 +75,8 @@ EXPORTS = (
     "pom_itb_check_dev", "pom_itb_check_batch",
     # include/pom_split.h
     "pom_itb_split_dev", "pom_itb_split_scratch", "pom_itb_split_headers", "pom_itb_split_batch",
+    # include/pom_sweep.h
+    "pom_itb_sweep_dev", "pom_itb_sweep_scratch", "pom_itb_sweep_header", "pom_itb_sweep_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
