@@ -396,3 +396,65 @@ void pom_layout_sweep(struct layout *L, const size_t *ids, size_t nb, size_t nlz
     K->o_pack = take(&o, POM_ALIGN_UP(K->pcap, 256));
     L->dtotal = o;
 }
+
+void pom_layout_unlink(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                       const size_t *cap, const struct req_spec *Q, size_t nreq, size_t blob_bytes, size_t scratch,
+                       size_t unlink_scratch, size_t enc_scratch)
+{
+    size_t in, out, o = 0, r = 0, payloads = 0, streams = 0;
+    layout_start(L, ids, nb, nlzo, src_len, cap, &in, &out);
+    struct itb_unlink_layout *K = &L->u.unlink;
+    struct req_layout *Y = &K->req;
+    for (size_t i = 0; i < nb; i++) {
+        const size_t dl = i < nlzo ? cap[ids[i]] : src_len[ids[i]];
+        payloads += POM_ALIGN_UP(dl, 16);
+        streams += pom_split_stream_room(dl);
+    }
+    Y->nreq = nreq;
+    Y->blob_bytes = blob_bytes;
+    L->o_srcoff = take(&o, 8 * nb);
+    L->o_dstoff = take(&o, 8 * nb);
+    Y->scan.o_scanoff = take(&o, 8 * nb);
+    K->o_edstoff = take(&o, 8 * nb);
+    K->o_pfrom = take(&o, 8 * nb);
+    K->o_pto = take(&o, 8 * nb);
+    K->o_hdr = take(&o, 32 * nb);
+    Y->o_req = take(&o, POM_REQ_SIZE * nreq);
+    L->o_srclen = take(&o, 4 * nb);
+    L->o_dstcap = take(&o, 4 * nb);
+    L->o_status = take(&o, 4 * nb);
+    L->o_outlen = take(&o, 4 * nb);
+    K->o_reqfirst = take(&o, 4 * (nb + 1));
+    K->o_edstcap = take(&o, 4 * nb);
+    K->o_plen = take(&o, 4 * nb);
+    Y->scan.o_adepth = take(&o, nb);
+    o = POM_ALIGN_UP(o, 256);
+    L->o_src = take(&o, in);
+    Y->o_blob = take(&o, POM_ALIGN_UP(blob_bytes, 256));
+    L->o_dst = o;
+    K->r_status = take(&r, 4 * nb);
+    K->r_outlen = take(&r, 4 * nb);
+    r = POM_ALIGN_UP(r, 8);
+    K->r_result = take(&r, 32 * nb);
+    K->r_elen = take(&r, 4 * nb);
+    K->r_est = take(&r, 4 * nb);
+    for (size_t w = 0; w < Q->nwords; w++)
+        Y->r_word[w] = take(&r, 4 * nreq);
+    Y->r_lease = r;
+    Y->res_hdr = POM_ALIGN_UP(r, 16);
+    Y->res_bytes = Y->res_hdr + Q->rec_fixed * nreq;
+    K->pcap = payloads;
+    Y->o_hres = o;
+    K->o_hrec = POM_ALIGN_UP(o + Y->res_bytes, 256);
+    L->htotal = K->o_hrec + K->pcap;
+    o += out;
+    L->o_scr = take(&o, POM_ALIGN_UP(scratch, 256));
+    K->o_sscr = take(&o, POM_ALIGN_UP(unlink_scratch, 256));
+    K->o_esrclen = take(&o, POM_ALIGN_UP(4 * nb, 256));
+    K->escr_bytes = enc_scratch;
+    K->o_escr = take(&o, POM_ALIGN_UP(enc_scratch, 256));
+    K->o_z = take(&o, POM_ALIGN_UP(streams, 256));
+    Y->o_res = take(&o, POM_ALIGN_UP(Y->res_bytes, 256));
+    K->o_pack = take(&o, POM_ALIGN_UP(K->pcap, 256));
+    L->dtotal = o;
+}

@@ -216,6 +216,34 @@ struct itb_sweep_layout {
     size_t o_pack, o_hrec;          /* device, host */
 };
 
+/* The ITB unlink: the request operations' staging -- the requests and the
+ * chunk's own blob among the inputs, four words and a 136-byte record a
+ * request among the results (struct req_layout comes first, so that
+ * pom_req_stage and pom_req_scatter serve this chunk too) -- with the sweep's
+ * writer half: among the inputs the header facts, each group's first request
+ * (u32, nb + 1), each stream slot and its size, and the three pack arrays,
+ * filled and uploaded once the results are back.  Device only: the unlink's
+ * scratch, the encoder's lengths and scratch, the stream slots, the packed
+ * output.  The results -- the decoders' two words, the 32-byte results, the
+ * encoder's out_len and status, then the requests' words and records -- lie
+ * alike on both sides and come back in one copy; what each record is stored
+ * as is decided from them, and exactly those bytes follow in a second one. */
+struct itb_unlink_layout {
+    struct req_layout req;          /* (no variable records: its o_first, rcap, o_pack and o_hrec stay 0) */
+    size_t o_hdr, o_reqfirst;       /* struct pom_check_hdr per block; u32, nb + 1 */
+    size_t o_edstoff, o_edstcap;    /* u64, u32 per block */
+    size_t o_pfrom, o_pto, o_plen;  /* u64, u64, u32 per block: the pack of what is delivered */
+    size_t o_sscr;                  /* device only */
+    size_t o_esrclen;               /* device only: u32 per block */
+    size_t o_escr, escr_bytes;
+    size_t o_z;                     /* device only: the stream slots */
+    size_t r_status, r_outlen;      /* i32, u32 per block: adjacent, in this order */
+    size_t r_result;                /* 32 bytes per block, 8-byte aligned */
+    size_t r_elen, r_est;           /* u32, i32 per block */
+    size_t pcap;                    /* room for the delivered payloads */
+    size_t o_pack, o_hrec;          /* device, host */
+};
+
 struct layout {
     size_t nb;
     const size_t *ids;
@@ -238,6 +266,7 @@ struct layout {
         struct itb_check_layout check;
         struct itb_split_layout split;
         struct itb_sweep_layout sweep;
+        struct itb_unlink_layout unlink;    /* (starts with the requests') */
     } u;
 };
 
@@ -275,6 +304,12 @@ size_t pom_split_stream_room(size_t n);
 /* sweep_scratch, enc_scratch: what the sweep and the encoder of nb blocks need. */
 void pom_layout_sweep(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
                       const size_t *cap, size_t scratch, size_t sweep_scratch, size_t enc_scratch);
+
+/* Q: the unlink's kind (fixed records, no lease); unlink_scratch, enc_scratch:
+ * what the unlink and the encoder of nb blocks need. */
+void pom_layout_unlink(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const size_t *src_len,
+                       const size_t *cap, const struct req_spec *Q, size_t nreq, size_t blob_bytes, size_t scratch,
+                       size_t unlink_scratch, size_t enc_scratch);
 
 /* The staging of a group of k single calls (host_single.c).  The header
  * arrays, then the inputs, lie alike on both sides and go up in one H2D copy

@@ -13,9 +13,11 @@
  * (itb_check.hip) has the walks' partition and fixed-size results; the ITB
  * split (itb_split.hip) has the check's partition, writes, and runs the encoder
  * over both halves behind it; the ITB sweep (itb_sweep.hip) is the split with
- * one payload and no second half.  Their
+ * one payload and no second half; the ITB unlink (itb_unlink.hip) is the
+ * request operations' staging and scatter with the sweep's writer half.  Their
  * callers (gc_scan.c, gc_stat.c, readdir.c, kvlist.c, column_codec.c, lookup.c,
- * kvget.c, check.c, itbsplit.c, itbsweep.c) select the blocks and put the results in the caller's order.
+ * kvget.c, check.c, itbsplit.c, itbsweep.c, unlink.c) select the blocks and put
+ * the results in the caller's order.
  */
 #include <pthread.h>
 #include <stdlib.h>
@@ -34,6 +36,7 @@
 #include "pom_lookup.h"
 #include "pom_split.h"
 #include "pom_sweep.h"
+#include "pom_unlink.h"
 
 /* Per block of a chunk with stored blocks: where the walk finds the payload
  * (decoded behind o_dst, or stored as staged behind o_src), the decoders'
@@ -1308,5 +1311,217 @@ int pom_itb_sweep_chunked(const uint8_t *const *src, const size_t *src_len, size
 {
     struct hbatch B = {.ops = &sw_ops, .src = src, .src_len = src_len, .status = sink->status, .is_lzo = sink->is_lzo,
                        .sink = sink};
+    return pom_host_batch(&B, nblocks);
+}
+
+/* ------------------------------------------------------------------------ */
+/* The ITB unlink: decode, check and unlink (itb_unlink.hip), encode          */
+/* ------------------------------------------------------------------------ */
+/* The request operations' partition, staging and scatter (an ITB and all its
+ * requests are in one chunk, the requests in block order and then the caller's
+ * own, renumbered to the chunk's ITB index, their names in a blob of the
+ * chunk's own) with the sweep's writer half.  Kernels on the chunk's stream:
+ * the decoders; pom_itb_unlink_dev, which applies each block's requests in
+ * order and rewrites its payload in place; the gather of the encoder's nb
+ * source lengths from the results; lzo_mi355x_compress_dev over the payloads
+ * where they lie.  The results (the decoders' words, the 32-byte results, the
+ * encoder's out_len and status, four words and a 136-byte record a request)
+ * come back in one copy queued behind the kernels.  Once they are back the
+ * host applies itb_lzo_compress's not-smaller rule, and the pack kernel
+ * gathers exactly what is delivered -- the stream, or the payload when it did
+ * not compress -- for the second D2H.  A block no request changed delivers no
+ * payload: its stored record is still right.  Staging: pom_layout_unlink
+ * (host_layout.h). */
+static size_t ul_cap(const struct hbatch *B, size_t b)
+{
+    const struct pom_unlink_sink *U = B->sink;
+    return U->K->cap[b];
+}
+
+static size_t ul_dl(const struct hbatch *B, size_t b)
+{
+    const struct pom_unlink_sink *U = B->sink;
+    return U->K->is_lzo[b] ? B->cap[b] : B->src_len[b];
+}
+
+/* the chunk budget counts the sweep's part and the requests' */
+static size_t ul_extra_cost(const struct hbatch *B, size_t b)
+{
+    const struct pom_unlink_sink *U = B->sink;
+    const struct pom_req_sink *K = U->K;
+    const size_t dl = K->is_lzo[b] ? K->cap[b] : B->src_len[b];
+    size_t blob = 0;
+    const size_t nreq = pom_req_block(K, b, &blob);
+    return 2 * dl + pom_split_stream_room(dl) + 256 + nreq * (POM_REQ_SIZE + 4 * K->spec->nwords + K->spec->rec_fixed) +
+           blob;
+}
+
+static void ul_layout(struct layout *L, const size_t *ids, size_t nb, size_t nlzo, const struct hbatch *B)
+{
+    const struct pom_unlink_sink *U = B->sink;
+    size_t nreq = 0, blob = 0;
+    for (size_t i = 0; i < nb; i++)
+        nreq += pom_req_block(U->K, ids[i], &blob);
+    pom_layout_unlink(L, ids, nb, nlzo, B->src_len, B->cap, U->K->spec, nreq, blob,
+                      lzo_mi355x_decompress_scratch((uint32_t)nlzo), pom_itb_unlink_scratch((uint32_t)nb),
+                      lzo_mi355x_compress_scratch((uint32_t)nb));
+}
+
+static int ul_stage(const struct layout *L, uint8_t *h, const struct hbatch *B)
+{
+    const struct pom_unlink_sink *U = B->sink;
+    const struct itb_unlink_layout *K = &L->u.unlink;
+    const size_t nb = L->nb;
+    struct pom_check_hdr *hd = (struct pom_check_hdr *)(h + K->o_hdr);
+    uint64_t *edo = (uint64_t *)(h + K->o_edstoff);
+    uint32_t *edc = (uint32_t *)(h + K->o_edstcap), *rf = (uint32_t *)(h + K->o_reqfirst);
+    size_t z = 0, at = 0;
+    if (nb > 0xFFFFFFFFu || pom_req_stage(L, h, U->K) != 0)
+        return -1;
+    pom_stage_inputs(L, h, B);
+    stage_scan(L, &K->req.scan, h, U->K->adepth);
+    memset(h + K->o_pfrom, 0, 8 * nb);
+    memset(h + K->o_pto, 0, 8 * nb);
+    memset(h + K->o_plen, 0, 4 * nb);
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = L->ids[i], room = pom_split_stream_room(ul_dl(B, b));
+        hd[i] = U->hdr[b];
+        rf[i] = (uint32_t)at;
+        at += U->K->req_first[b + 1] - U->K->req_first[b];
+        edo[i] = K->o_z + z;
+        edc[i] = (uint32_t)room;
+        z += room;
+    }
+    rf[nb] = (uint32_t)at;
+    return 0;
+}
+
+static int ul_kernels(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct pom_unlink_sink *U = B->sink;
+    const struct itb_unlink_layout *K = &L->u.unlink;
+    const struct req_layout *Y = &K->req;
+    uint8_t *d = S->dmem, *res = d + Y->o_res;
+    const uint32_t nb = (uint32_t)L->nb;
+    struct pom_unlink_result *result = (struct pom_unlink_result *)(res + K->r_result);
+    if (pom_decode_lzo_blocks(S, L, 0) != 0)
+        return -1;
+    if (pom_itb_unlink_dev(d, (const uint64_t *)(d + Y->scan.o_scanoff), (const uint32_t *)(d + L->o_outlen),
+                           (const int32_t *)(d + L->o_status), d + Y->scan.o_adepth,
+                           (const struct pom_check_hdr *)(d + K->o_hdr), nb, U->async_unlink,
+                           (const struct pom_lookup_req *)(d + Y->o_req), (const uint32_t *)(d + K->o_reqfirst),
+                           (uint32_t)Y->nreq, d + Y->o_blob, (uint32_t)Y->blob_bytes,
+                           (int32_t *)(res + Y->r_word[RW_ERR]), (uint32_t *)(res + Y->r_word[RW_NR]),
+                           (uint32_t *)(res + Y->r_word[RW_DEPTH]), (uint32_t *)(res + Y->r_word[RW_LEN]),
+                           res + Y->res_hdr, result, d + K->o_sscr, S->stream) != 0)
+        return -1;
+    if (lzo_mi355x_launch_itb_unlink_lens(result, nb, (uint32_t *)(d + K->o_esrclen), S->stream) != 0)
+        return -1;
+    if (lzo_mi355x_compress_dev(d, (const uint64_t *)(d + Y->scan.o_scanoff), (const uint32_t *)(d + K->o_esrclen), d,
+                                (const uint64_t *)(d + K->o_edstoff), (const uint32_t *)(d + K->o_edstcap),
+                                (uint32_t *)(res + K->r_elen), (int32_t *)(res + K->r_est), nb, d + K->o_escr,
+                                S->stream) != 0)
+        return -1;
+    /* status, then out_len: adjacent among the inputs and among the results */
+    if (hipMemcpyAsync(res + K->r_status, d + L->o_status, 8 * L->nb, hipMemcpyDeviceToDevice, S->stream) != hipSuccess)
+        return -1;
+    return hipMemcpyAsync(S->hmem + Y->o_hres, res, Y->res_bytes, hipMemcpyDeviceToHost, S->stream) == hipSuccess
+               ? 0 : -1;
+}
+
+/* Block i of the chunk as it is delivered: the bytes, and whether they are its stream. */
+static size_t ul_payload(const struct layout *L, const uint8_t *h, size_t i, int *lzo)
+{
+    const struct itb_unlink_layout *K = &L->u.unlink;
+    const uint8_t *res = h + K->req.o_hres;
+    struct pom_unlink_result r;
+    memcpy(&r, res + K->r_result + sizeof r * i, sizeof r);
+    const uint32_t z = ((const uint32_t *)(res + K->r_elen))[i];
+    *lzo = 0;
+    if (r.err != 0 || r.changed == 0 || r.len < POM_ITB_SIZE)
+        return 0;
+    *lzo = z < r.len - (POM_ITB_SIZE - POM_ITB_ITE_OFF);
+    return *lzo ? z : r.len - (POM_ITB_SIZE - POM_ITB_ITE_OFF);
+}
+
+static int ul_collect(struct slot *S, const struct layout *L, const struct hbatch *B, size_t *packed)
+{
+    const struct itb_unlink_layout *K = &L->u.unlink;
+    uint8_t *d = S->dmem, *h = S->hmem;
+    const size_t nb = L->nb;
+    uint64_t *pf = (uint64_t *)(h + K->o_pfrom), *pt = (uint64_t *)(h + K->o_pto);
+    uint32_t *pl = (uint32_t *)(h + K->o_plen);
+    const uint64_t *eso = (const uint64_t *)(h + K->req.scan.o_scanoff), *edo = (const uint64_t *)(h + K->o_edstoff);
+    const int32_t *est = (const int32_t *)(h + K->req.o_hres + K->r_est);
+    size_t total = 0;
+    (void)B;
+    for (size_t i = 0; i < nb; i++) {
+        int lzo;
+        const size_t n = ul_payload(L, h, i, &lzo);
+        if (n && est[i] != 0)
+            return -1;                              /* (the slots hold any stream: the encoder cannot fail) */
+        pf[i] = lzo ? edo[i] : eso[i];
+        pt[i] = total;
+        pl[i] = (uint32_t)n;
+        total += POM_ALIGN_UP(n, 16);
+    }
+    if (total > K->pcap)
+        return -1;
+    if (total &&
+        (hipMemcpyAsync(d + K->o_pfrom, pf, 16 * nb, hipMemcpyHostToDevice, S->stream) != hipSuccess ||
+         hipMemcpyAsync(d + K->o_plen, pl, 4 * nb, hipMemcpyHostToDevice, S->stream) != hipSuccess ||
+         lzo_mi355x_launch_pack(d, (const uint64_t *)(d + K->o_pfrom), (const uint32_t *)(d + K->o_plen),
+                                (const uint32_t *)(d + K->o_plen), (const uint64_t *)(d + K->o_pto), d + K->o_pack,
+                                (uint32_t)nb, S->stream) != 0 ||
+         hipMemcpyAsync(h + K->o_hrec, d + K->o_pack, total, hipMemcpyDeviceToHost, S->stream) != hipSuccess))
+        return -1;
+    *packed = total;
+    return 0;
+}
+
+static int ul_unpack(struct slot *S, const struct layout *L, const struct hbatch *B)
+{
+    const struct pom_unlink_sink *U = B->sink;
+    const struct itb_unlink_layout *K = &L->u.unlink;
+    const uint8_t *h = S->hmem, *res = h + K->req.o_hres;
+    const size_t nb = L->nb;
+    const int32_t *st = (const int32_t *)(res + K->r_status);
+    const uint32_t *ol = (const uint32_t *)(res + K->r_outlen);
+    const uint64_t *pt = (const uint64_t *)(h + K->o_pto);
+    pom_req_scatter(L, h, U->K, NULL, 0);
+    for (size_t i = 0; i < nb; i++) {
+        const size_t b = L->ids[i], to = U->idx[b];
+        struct pom_unlink_result *r = &U->result[to];
+        int lzo;
+        const size_t n = ul_payload(L, h, i, &lzo);
+        U->status[b] = st[i];
+        U->out_len[b] = ol[i];
+        U->delivered[b] = 1;
+        memcpy(r, res + K->r_result + sizeof *r * i, sizeof *r);
+        U->err[to] = r->err;
+        U->rec_len[to] = 0;
+        if (r->err != 0 || r->changed == 0)
+            continue;
+        if (POM_ITBH_SIZE + n > U->out_cap[to]) {
+            U->err[to] = LZO_E_OUTPUT_OVERRUN;
+            continue;
+        }
+        if (pom_itb_unlink_header(U->rec_hdr[b], r, lzo ? (uint32_t)n : POM_SPLIT_NO_STREAM, U->out[to]) < 0)
+            return -1;
+        memcpy(U->out[to] + POM_ITBH_SIZE, h + K->o_hrec + pt[i], n);
+        U->rec_len[to] = POM_ITBH_SIZE + n;
+    }
+    return 0;
+}
+
+/* (an undelivered ITB: the caller sees it in `delivered`; its requests keep what pom_req_begin put there) */
+static const struct chunk_ops ul_ops = {"itb unlink", 0, ul_cap, ul_extra_cost, NULL, ul_layout,
+                                        ul_stage, ul_kernels, ul_collect, ul_unpack};
+
+int pom_itb_unlink_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                           struct pom_unlink_sink *sink)
+{
+    struct hbatch B = {.ops = &ul_ops, .src = src, .src_len = src_len, .status = sink->K->status,
+                       .is_lzo = sink->K->is_lzo, .sink = sink};
     return pom_host_batch(&B, nblocks);
 }

@@ -85,6 +85,11 @@ const struct req_spec pom_req_lookup = {
     .o_itb = offsetof(struct pom_lookup_req, itb), .o_blob = offsetof(struct pom_lookup_req, name_off),
     .o_len = offsetof(struct pom_lookup_req, namelen), .len_bytes = 2, .len_max = 255,
     .nwords = RW_DEPTH + 1, .rec_fixed = POM_LK_REC_SIZE};
+/* unlink: the lookup's request and record, and a fourth word, `what` */
+const struct req_spec pom_req_unlink = {
+    .o_itb = offsetof(struct pom_lookup_req, itb), .o_blob = offsetof(struct pom_lookup_req, name_off),
+    .o_len = offsetof(struct pom_lookup_req, namelen), .len_bytes = 2, .len_max = 255,
+    .nwords = RW_LEN + 1, .rec_fixed = POM_LK_REC_SIZE};
 const struct req_spec pom_req_kvget = {
     .o_itb = offsetof(struct pom_kvget_req, itb), .o_blob = offsetof(struct pom_kvget_req, skey_off),
     .o_len = offsetof(struct pom_kvget_req, sklen), .len_bytes = 4, .len_max = POM_KV_VALUE_MAX,

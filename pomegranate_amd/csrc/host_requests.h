@@ -44,8 +44,9 @@ size_t pom_group_requests(const size_t *key, size_t nreq, size_t m, size_t *firs
 /* The two kinds.  Lookup: namelen <= 255 and the name inside the blob; results
  * err, nr, depth and a 136-byte record.  Get: POM_KV_STR set, sklen <= 320 and
  * the key inside the blob; results err, nr, depth, len, lease and a record of
- * at most 364 bytes. */
-extern const struct req_spec pom_req_lookup, pom_req_kvget;
+ * at most 364 bytes.  Unlink (include/pom_unlink.h): the lookup's request and
+ * record; results err, nr, depth and `what`, in RW_LEN's place. */
+extern const struct req_spec pom_req_lookup, pom_req_kvget, pom_req_unlink;
 
 /* One call's requests and results as its chunks see them (pom_lookup_chunked,
  * pom_kvget_chunked): block b's requests are req[req_ids[k]] for k in

@@ -86,10 +86,11 @@ ITB_SCAN_FN bool itb_find_name_eq(const uint8_t* ite, const uint8_t* name, uint3
     return true;
 }
 
-// ite_match (mds/itb.c:1119-1148) on an ITE that lies inside the payload.
-ITB_SCAN_FN bool itb_find_match(const uint8_t* ite, const pom_lookup_req& q, const uint8_t* names)
+// ite_match (mds/itb.c:1119-1148) on an ITE that lies inside the payload, with
+// its flag and namelen words given as fn (a writer keeps the flags its earlier
+// requests changed outside the payload: itb_unlink.h).
+ITB_SCAN_FN bool itb_find_match_fn(const uint8_t* ite, uint64_t fn, const pom_lookup_req& q, const uint8_t* names)
 {
-    const uint64_t fn = itb_scan_ld64(ite + POM_ITE_FLAG_OFF);      // flag, namelen
     const uint32_t state = (uint32_t)fn & POM_ITE_STATE_MASK;
     if ((q.flag & POM_LK_ITE_SHADOW) && state != POM_ITE_SHADOW && state != POM_ITE_UNLINKED)
         return false;
@@ -102,6 +103,11 @@ ITB_SCAN_FN bool itb_find_match(const uint8_t* ite, const pom_lookup_req& q, con
     if (q.flag & POM_LK_BY_NAME)
         return (uint32_t)(fn >> 32) == q.namelen && itb_find_name_eq(ite, names + q.name_off, q.namelen);
     return false;
+}
+
+ITB_SCAN_FN bool itb_find_match(const uint8_t* ite, const pom_lookup_req& q, const uint8_t* names)
+{
+    return itb_find_match_fn(ite, itb_scan_ld64(ite + POM_ITE_FLAG_OFF), q, names);     // flag, namelen
 }
 
 // ---------------------------------------------------------------------------

@@ -442,6 +442,54 @@ struct pom_sweep_sink {
 int pom_itb_sweep_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
                           struct pom_sweep_sink *sink);
 
+/* The ITB unlink (itb_unlink.hip): the second launch of pom_itb_unlink_dev of
+ * include/pom_unlink.h, behind the check's, whose reports and err it reads.
+ * payload is 16-byte aligned, req and out 8-byte aligned; the caller has seen
+ * to hdr. */
+struct pom_unlink_result;
+int lzo_mi355x_launch_itb_unlink(uint8_t *payload, const uint64_t *payload_off, const uint32_t *payload_len,
+                                 const uint8_t *adepth, const struct pom_check_hdr *hdr, uint32_t nitb,
+                                 int async_unlink, const struct pom_lookup_req *req, const uint32_t *req_first,
+                                 uint32_t nreq, const uint8_t *names, uint32_t names_len,
+                                 const struct pom_check_report *ck_report, const int32_t *ck_err, int32_t *err,
+                                 uint32_t *nr, uint32_t *depth, uint32_t *what, uint8_t *out,
+                                 struct pom_unlink_result *result, hipStream_t stream);
+
+/* The encoder's source lengths of nitb payloads from the unlink's results on
+ * the device: len[b] = result[b].len - 264, 0 where nothing is produced. */
+int lzo_mi355x_launch_itb_unlink_lens(const struct pom_unlink_result *result, uint32_t nitb, uint32_t *len,
+                                      hipStream_t stream);
+
+/* Host side (host_records.c), not part of the ABI: the request operations'
+ * pipeline (requests grouped by ITB, renumbered and staged with their names,
+ * fixed results scattered into the caller's request order: K, set up by
+ * pom_req_begin with the unlink's kind) with the sweep's writer half behind
+ * it: the check, the unlink and the encoder of the one payload behind each
+ * chunk's decode.  Block k of the call is the caller's record idx[k], whose
+ * header is rec_hdr[k] (264 bytes).  A delivered block gets status[k],
+ * out_len[k], its result at result[idx[k]], err[idx[k]] (the result's err, or
+ * LZO_E_OUTPUT_OVERRUN when the record does not fit out_cap), and, when
+ * something changed and the record fits, the stored record in out with its
+ * length.  A block whose chunk is not delivered keeps what the caller put
+ * there. */
+struct pom_unlink_sink {
+    struct pom_req_sink *K;
+    int async_unlink;
+    const struct pom_check_hdr *hdr;    /* per block */
+    const uint8_t *const *rec_hdr;      /* per block */
+    const size_t *idx;
+    int32_t *status;                    /* per block: the decoder's */
+    uint32_t *out_len;
+    uint8_t *delivered;                 /* per block: 1 once its chunk is delivered */
+    uint8_t *const *out;                /* the caller's, in the caller's order */
+    const size_t *out_cap;
+    size_t *rec_len;
+    struct pom_unlink_result *result;
+    int *err;
+};
+int pom_itb_unlink_chunked(const uint8_t *const *src, const size_t *src_len, size_t nblocks,
+                           struct pom_unlink_sink *sink);
+
 /* Host side (host_records.c), not part of the ABI: pom_gc_scan_chunked's
  * pipeline (LZO records decoded, stored ones checked as staged) with the check
  * behind each chunk's decode.  Block k of the call is the caller's record

@@ -77,6 +77,8 @@ EXPORTS = (
     "pom_itb_split_dev", "pom_itb_split_scratch", "pom_itb_split_headers", "pom_itb_split_batch",
     # include/pom_sweep.h
     "pom_itb_sweep_dev", "pom_itb_sweep_scratch", "pom_itb_sweep_header", "pom_itb_sweep_batch",
+    # include/pom_unlink.h
+    "pom_itb_unlink_dev", "pom_itb_unlink_scratch", "pom_itb_unlink_header", "pom_itb_unlink_batch",
 )
 
 _lib: Optional[ctypes.CDLL] = None
